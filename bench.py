@@ -11,6 +11,11 @@ exactly the control-loop Hz at K=4096, H=20).
 Protocol: W untimed warm-up iterations, then EXACTLY K timed ones bracketed by barrier +
 torch.cuda.synchronize(); `value` = K / elapsed (max over ranks); the per-iteration wall times of the same run give
 median / p5 / p95.  Prints ONE JSON line (rank 0).  DESIGN.md "Measurement" defines roofline / cpu_baseline.
+
+A plain run does only that: set-up, warm-up, the timed iterations, the result line.  Everything else the benchmark measures or
+checks - HBM ceiling, per-kernel hipEvent times and roofline, the shipped-conf and strong-scaling rows, the reference-API loops,
+task outcome and final-state sanity, the exchange timing and per-rank reports, the mailbox A/B pass, the CPU baseline - runs
+with --full.  --dump-outputs DIR writes what the last timed iteration computed as DIR/<name>.npy (float32).
 """
 import argparse
 import ctypes
@@ -376,6 +381,19 @@ def time_sampler(loop, n=20):
     return e0.elapsed_time(e1) / n
 
 
+def dump_outputs(loop, out_dir):
+    """--dump-outputs: what a caller of the timed loop has after its last iteration, as float32 DIR/<name>.npy - the action on the
+    host, the nominal control sequence the next iteration starts from, the costs of the K rollouts, the K = 1 world's state"""
+    os.makedirs(out_dir, exist_ok=True)
+    loop.torch.cuda.synchronize()
+    mppi, world = loop.planner.mppi, loop.world
+    world._materialise()
+    arrays = {"action": loop.action, "nominal_u": mppi.U.numpy(), "rollout_costs": mppi.get_costs().numpy(),
+              "world_dof_state": world._dof_state[0].cpu().numpy(), "world_root_state": world._root_state[0].cpu().numpy()}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def cpu_baseline(loop, budget_s=24.0):
     """CPU rows beside the GPU number, on this box's host cores, bounded to ~budget_s of CPU work.  Every row runs in its own
     process (oracle/cpu_pipeline.py) so that thread counts and the OpenMP wait policy are fixed before any runtime starts:
@@ -612,6 +630,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)     # 20 warm-up + 200 timed iterations
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure (roofline, per-kernel times, shipped-conf and "
+                         "strong-scaling rows, reference-API loops, task outcome, exchange reports, mailbox A/B, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed iteration computed (action, nominal controls, rollout costs, world state) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-facade", action="store_true", help="skip the reference-API loops (value_facade, value_generic_objective)")
     ap.add_argument("--async-loop", action="store_true", help="do not wait for the action on the host every iteration")
@@ -684,7 +707,7 @@ def main():
 
     hbm = {}
 
-    def measure(name, k_per_gpu, steps, warmup, shipped=False, env=env, ceiling=False):
+    def measure(name, k_per_gpu, steps, warmup, shipped=False, env=env, ceiling=False, profile=True, dump_to=None):
         loop = Loop(name, k_per_gpu, env, sync=sync, shipped=shipped)
         if ceiling:  # (between the construction of the loop - host work, the device idles - and its timed run)
             hbm["measured"] = hbm_copy_ceiling(torch, float(os.environ.get("MPPI_BENCH_CEILING_MS", "20")))
@@ -695,8 +718,10 @@ def main():
             for _ in range(3):
                 loop.iterate()     # lazy initialisation (RCCL channels, LDS limits) must not happen under capture
             graphed = loop.capture()
-        elapsed, per_iter, kms = loop.run(steps, warmup)
-        if graphed:
+        elapsed, per_iter, kms = loop.run(steps, warmup, profile=profile)
+        if dump_to is not None:    # (before the eager profiling pass below moves the closed loop on)
+            dump_outputs(loop, dump_to)
+        if graphed and profile:
             kms = loop.profile_kernels()
         return loop, elapsed, per_iter, kms, graphed
 
@@ -723,75 +748,80 @@ def main():
         del l2
         return row
 
-    loop, elapsed, per_iter, kms, graphed = measure(args.workload, K_PER_GPU, args.steps, args.warmup, ceiling=True)
-    exchange_ms = loop.time_exchange() if sharded else None   # (every rank takes part)
-    reports = gather_reports(loop)
+    # a plain run: no HBM ceiling in front of the timed run, no hipEvent brackets inside it (--full: both, as the roofline needs them)
+    loop, elapsed, per_iter, kms, graphed = measure(args.workload, K_PER_GPU, args.steps, args.warmup, ceiling=args.full, profile=args.full,
+                                                    dump_to=args.dump_outputs if rank == 0 else None)
+    exchange_ms = loop.time_exchange() if sharded and args.full else None   # (every rank takes part)
+    reports = gather_reports(loop) if args.full else None
     # SURVEY 8e's scaling argument is made on BASELINE configs[4] (compute >> exchange): its strong-scaling row is timed in
     # the same job at every N, the weak row (4096 panda samples per GPU) being the line's own `value`
     second = None
-    if args.workload == "panda_reach" and not args.k_total and os.environ.get("MPPI_BENCH_SECOND", "1") != "0":
+    if args.full and args.workload == "panda_reach" and not args.k_total and os.environ.get("MPPI_BENCH_SECOND", "1") != "0":
         second = strong_row()
 
     # the same workload with the conf file AS THE REFERENCE SHIPS IT (filter_u: True in conf/mppi/panda.yaml:22): the smoothing
     # operator U <- F U runs inside the same combine kernel, the iteration costs the same
     shipped = None
-    if os.environ.get("MPPI_BENCH_SHIPPED", "1") != "0":
+    if args.full and os.environ.get("MPPI_BENCH_SHIPPED", "1") != "0":
         ls, es, ps, ks, gs = measure(args.workload, K_PER_GPU, max(20, args.steps // 2), min(args.warmup, 10), shipped=True)
         shipped = {"value": world_size * len(ps) / es, "ms_per_step": 1e3 * es / len(ps), "filter_u": bool(ls.cfg.mppi.filter_u),
                    "steps": len(ps), "graph": gs}
         del ls
 
-    # final state sanity (default workload): the closed loop must have moved the end effector to the goal
-    world = loop.world
-    world._materialise()
-    dist_to_goal = None
-    final_root = [round(float(v), 4) for v in world._root_state[0, :, 0:3].reshape(-1).cpu().numpy()]  # actor positions: run-to-run sanity
-    if args.workload == "panda_reach":
-        ee = world.get_actor_link_by_name("panda", "panda_ee_tip")[0, 0:3].cpu().numpy()
-        dist_to_goal = float(np.linalg.norm(ee - np.asarray(wl["goal"])))
-    # task outcome of the contact workloads (what their Objectives drive down: examples/boxer_push/planner.py:26-67,
-    # examples/panda_pick/planner.py:24-53) after the warm-up + timed iterations of this run
-    outcome = None
-    if args.workload in ("boxer_push", "panda_pick"):
-        o = loop.objective
-        pos = lambda name: world.get_actor_position_by_name(name)[0, 0:3].cpu().numpy()
-        ee = world.get_actor_link_by_name(o.robot, o.link)[0, 0:3].cpu().numpy()
-        nd = 2 if args.workload == "boxer_push" else 3
-        outcome = {"final_block_to_goal_m": float(np.linalg.norm((pos(o.block) - pos(o.goal))[:nd])),
-                   "final_ee_to_block_m": float(np.linalg.norm((ee - pos(o.block))[:nd])),
-                   "iterations": args.steps + args.warmup, "dims": nd}
-        if args.workload == "panda_pick":
-            # (round 6: the one-gram block is held implicitly by the links that touch it, DESIGN.md 3 "light bodies"; whether THIS run's
-            # few hundred iterations got as far as lifting it is in the height - tests/test_gpu_task_outcomes.py runs the task to its end)
-            table = next((a for a in world.scene.env_cfg if a.name == o.table), None)
-            blk = next((a for a in world.scene.env_cfg if a.name == o.block), None)
-            if table is not None and blk is not None:
-                outcome["final_block_height_above_table_m"] = float(pos(o.block)[2] - (pos(o.table)[2] + 0.5 * table.size[2] + 0.5 * blk.size[2]))
-        if args.workload == "boxer_push":
-            # the goal of the reference's pushing examples sits INSIDE the footprint of paper_obst1 (both at (1, 1): reference
-            # examples/boxer_push/config_boxer_push.yaml, conf/actors/paper_obst1.yaml): the block is done when it rests against that
-            # obstacle - the distance it can reach is the obstacle's and its own half extent, not zero (tools/task_outcomes.py)
-            obst = next((a for a in world.scene.env_cfg if a.name == o.obstacles[0]), None)
-            blk = next((a for a in world.scene.env_cfg if a.name == o.block), None)
-            d = pos(o.goal)[:2] - pos(o.obstacles[0])[:2]
-            if obst is not None and blk is not None and abs(d[0]) < 0.5 * obst.size[0] and abs(d[1]) < 0.5 * obst.size[1]:
-                outcome["goal_is_inside_the_footprint_of"] = o.obstacles[0]
-                outcome["closest_the_block_can_get_m"] = float(0.5 * min(obst.size[0], obst.size[1]) + 0.5 * min(blk.size[0], blk.size[1]))
+    dist_to_goal, final_root, outcome = None, None, None
+    if args.full:
+        # final state sanity (default workload): the closed loop must have moved the end effector to the goal
+        world = loop.world
+        world._materialise()
+        final_root = [round(float(v), 4) for v in world._root_state[0, :, 0:3].reshape(-1).cpu().numpy()]  # actor positions: run-to-run sanity
+        if args.workload == "panda_reach":
+            ee = world.get_actor_link_by_name("panda", "panda_ee_tip")[0, 0:3].cpu().numpy()
+            dist_to_goal = float(np.linalg.norm(ee - np.asarray(wl["goal"])))
+        # task outcome of the contact workloads (what their Objectives drive down: examples/boxer_push/planner.py:26-67,
+        # examples/panda_pick/planner.py:24-53) after the warm-up + timed iterations of this run
+        if args.workload in ("boxer_push", "panda_pick"):
+            o = loop.objective
+            pos = lambda name: world.get_actor_position_by_name(name)[0, 0:3].cpu().numpy()
+            ee = world.get_actor_link_by_name(o.robot, o.link)[0, 0:3].cpu().numpy()
+            nd = 2 if args.workload == "boxer_push" else 3
+            outcome = {"final_block_to_goal_m": float(np.linalg.norm((pos(o.block) - pos(o.goal))[:nd])),
+                       "final_ee_to_block_m": float(np.linalg.norm((ee - pos(o.block))[:nd])),
+                       "iterations": args.steps + args.warmup, "dims": nd}
+            if args.workload == "panda_pick":
+                # (round 6: the one-gram block is held implicitly by the links that touch it, DESIGN.md 3 "light bodies"; whether THIS run's
+                # few hundred iterations got as far as lifting it is in the height - tests/test_gpu_task_outcomes.py runs the task to its end)
+                table = next((a for a in world.scene.env_cfg if a.name == o.table), None)
+                blk = next((a for a in world.scene.env_cfg if a.name == o.block), None)
+                if table is not None and blk is not None:
+                    outcome["final_block_height_above_table_m"] = float(pos(o.block)[2] - (pos(o.table)[2] + 0.5 * table.size[2] + 0.5 * blk.size[2]))
+            if args.workload == "boxer_push":
+                # the goal of the reference's pushing examples sits INSIDE the footprint of paper_obst1 (both at (1, 1): reference
+                # examples/boxer_push/config_boxer_push.yaml, conf/actors/paper_obst1.yaml): the block is done when it rests against that
+                # obstacle - the distance it can reach is the obstacle's and its own half extent, not zero (tools/task_outcomes.py)
+                obst = next((a for a in world.scene.env_cfg if a.name == o.obstacles[0]), None)
+                blk = next((a for a in world.scene.env_cfg if a.name == o.block), None)
+                d = pos(o.goal)[:2] - pos(o.obstacles[0])[:2]
+                if obst is not None and blk is not None and abs(d[0]) < 0.5 * obst.size[0] and abs(d[1]) < 0.5 * obst.size[1]:
+                    outcome["goal_is_inside_the_footprint_of"] = o.obstacles[0]
+                    outcome["closest_the_block_can_get_m"] = float(0.5 * min(obst.size[0], obst.size[1]) + 0.5 * min(blk.size[0], blk.size[1]))
     # the loop a user of the reference runs (MPPIisaacPlanner.compute_action_tensor with torch.save blobs, a K = 1 world stepped from
     # Python): with the example's Objective fused, and with a reference-style Python compute_cost (generic mode)
     facade = None
-    if world_size == 1 and not args.no_facade and os.environ.get("MPPI_BENCH_FACADE", "1") != "0":
+    if args.full and world_size == 1 and not args.no_facade and os.environ.get("MPPI_BENCH_FACADE", "1") != "0":
         facade = facade_rows(args.workload, loop.cfg.mppi.device)
 
     if rank == 0:
         loop_hz = args.steps / elapsed
         K, H, nu = loop.K, loop.H, loop.nu
         lat = per_iter * 1e3
-        info = ctypes.create_string_buffer(256)
-        loop.capi.check(loop.lib, loop.lib.mppi_kernel_info(loop.P, info, 256))
-        info = dict(kv.split("=") for kv in info.value.decode().split())
-        n_waves = int(info["waves"])
-        sampler_ms = time_sampler(loop) if loop.planner.sim._mppi_config.sampling == 0 else None
+        halton = loop.planner.sim._mppi_config.sampling == 0
+        sampler_ms = time_sampler(loop) if args.full and halton else None
+        roof = None
+        if args.full:
+            info = ctypes.create_string_buffer(256)
+            loop.capi.check(loop.lib, loop.lib.mppi_kernel_info(loop.P, info, 256))
+            info = dict(kv.split("=") for kv in info.value.decode().split())
+            roof = roofline(loop, kms[0], hbm["measured"], int(info["waves"]))
         out = {
             "metric": "MPPI control-loop Hz (K samples x H horizon), Panda 7-DoF K=4096 H=20" if (args.workload == "panda_reach" and K == 4096)
                       else f"MPPI control-loop Hz, {args.workload} K={K} H={H} (not the BASELINE metric)",
@@ -816,8 +846,9 @@ def main():
                                        + (f"mailbox exchange (library kernels: store into every rank's inbox, poll the own one) of {loop.n_gathered} records"
                                           if loop.exchange == "mailbox" else f"in-place {backend} all-gather of {loop.n_records} folded records") + " -> combine"
                                        + (" (one captured HIP graph per iteration)" if graphed else "")) if sharded else "single GPU",
-                       "noise": ("fixed halton-spline set, sampled once at construction (k_sample %.1f us, outside the loop)" % (1e3 * sampler_ms))
-                                if sampler_ms is not None else "gaussian, redrawn on the device every iteration",
+                       "noise": ("fixed halton-spline set, sampled once at construction (k_sample %.1f us, outside the loop)" % (1e3 * sampler_ms)
+                                 if sampler_ms is not None else "fixed halton-spline set, sampled once at construction (outside the loop)")
+                                if halton else "gaussian, redrawn on the device every iteration",
                        "loop_hz": loop_hz, "env_steps_per_s": loop_hz * K * H * world_size,
                        "final_ee_to_goal_m": dist_to_goal, "final_actor_positions": final_root, "task_outcome": outcome,
                        "facade": {"what": "the reference's own loop (examples/<x>/world.py:32-50): torch.save blobs through "
@@ -832,10 +863,11 @@ def main():
                        "exchange": {"selected": loop.exchange, "why": loop.exchange_why, "exchange_ms": exchange_ms, "per_rank": reports} if sharded else None,
                        "shipped_conf": shipped,
                        "cfg5_strong": second},
-            "roofline": roofline(loop, kms[0], hbm["measured"], n_waves),
-            "kernels_ms": {"k_rollout(+record tail)": kms[0], "k_reduce(generic mode only)": kms[1], "k_combine_update(+world step)": kms[2]},
+            "roofline": roof,
+            "kernels_ms": {"k_rollout(+record tail)": kms[0], "k_reduce(generic mode only)": kms[1], "k_combine_update(+world step)": kms[2]}
+                          if args.full else None,
         }
-        if world_size == 1 and not args.no_cpu_baseline:
+        if args.full and world_size == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(loop)
         ctypes.CDLL(None).fflush(None)  # (C stdio of the libraries: out through the redirected fd before it is restored)
         sys.stdout.flush()
@@ -846,7 +878,7 @@ def main():
     # any refusal keeps RCCL and says why).  Its numbers go to stderr and gpurun_out/ - they are evidence, not the metric.
     # (MPPI_BENCH_MAILBOX_AB=force: also with gloo staging - ranks sharing one device, tests/test_bench_contract.py)
     ab_mode = os.environ.get("MPPI_BENCH_MAILBOX_AB", "1")
-    if world_size > 1 and (backend == "nccl" or ab_mode == "force") and exchange == "rccl" and ab_mode != "0":
+    if args.full and world_size > 1 and (backend == "nccl" or ab_mode == "force") and exchange == "rccl" and ab_mode != "0":
         env_mb = dict(env, exchange="mailbox")
         try:
             lm, em, pm, km, gm = measure(args.workload, K_PER_GPU, max(20, args.steps // 2), min(args.warmup, 10), env=env_mb)

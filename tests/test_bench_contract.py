@@ -20,7 +20,7 @@ def run_bench(*extra):
 
 
 def test_bench_prints_one_json_line_with_the_contract_keys():
-    d = run_bench()
+    d = run_bench("--full")
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
                 "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in d, key
@@ -54,8 +54,29 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
     assert d["value_generic_objective"] >= 0.7 * d["value_facade"] and d["value_generic_objective_untraced"] == f["generic_untraced"]["value"]
 
 
+def test_plain_bench_is_the_headline_alone_and_dumps_what_it_computed(tmp_path):
+    """without --full: the headline keys, nothing measured beside them; --dump-outputs writes the last timed iteration's arrays as
+    float32 .npy files, and the same arguments give the same inputs - so the same arrays - from run to run"""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = run_bench("--dump-outputs", str(tmp_path / str(i)))
+        assert d["steps"] == 60 and d["warmup"] == 10 and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert "Panda 7-DoF K=4096 H=20" in d["metric"] and d["value"] > 100.0
+        assert d["value"] == pytest.approx(1e3 / d["ms_per_step"], rel=1e-6)
+        assert d["roofline"] is None and d["kernels_ms"] is None and d["value_facade"] is None and "cpu_baseline" not in d
+        files = sorted(os.listdir(tmp_path / str(i)))
+        assert files == ["action.npy", "nominal_u.npy", "rollout_costs.npy", "world_dof_state.npy", "world_root_state.npy"], files
+        arrays = {f: np.load(tmp_path / str(i) / f) for f in files}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+        assert arrays["action.npy"].shape == (7,) and arrays["nominal_u.npy"].shape == (20, 7) and arrays["rollout_costs.npy"].shape == (4096,)
+        dumps.append(arrays)
+    for f in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][f], dumps[1][f], err_msg=f)
+
+
 def test_bench_other_workloads_and_the_sharded_code_path():
-    d = run_bench("--workload", "boxer_push", "--no-cpu-baseline")
+    d = run_bench("--full", "--workload", "boxer_push", "--no-cpu-baseline")
     assert "boxer_push" in d["metric"] and d["roofline"]["kernel"] == "k_rollout_scene_quad" and d["value"] > 10
     # the contact workloads' lines carry their task outcome, and what the numbers mean: the goal of the pushing scene lies inside an
     # obstacle's footprint (the block is done when it rests against it)
@@ -78,7 +99,7 @@ def test_bench_two_ranks_launched_like_the_driver_does():
     exchange goes over gloo (MPPI_BENCH_BACKEND); on the 8-GPU node the same code runs over RCCL."""
     env = dict(os.environ, MPPI_BENCH_BACKEND="gloo")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                          "--master-port", "29613", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "100", "--warmup", "10"],
+                          "--master-port", "29613", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "100", "--warmup", "10", "--full"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = out.stdout.strip().splitlines()
@@ -95,7 +116,7 @@ def test_plain_python_bench_gpus_2_launches_its_own_ranks():
     bench.py becomes the launcher - two ranks on 127.0.0.1, ONE valid result line on stdout"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(MPPI_BENCH_BACKEND="gloo", MPPI_BENCH_SECOND="0", MPPI_BENCH_SHIPPED="0")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "60", "--warmup", "10"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "60", "--warmup", "10", "--full"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = out.stdout.strip().splitlines()
@@ -113,7 +134,7 @@ def test_plain_python_bench_gpus_8_as_the_driver_will_run_it():
     from every rank, and the mailbox A/B pass that follows the result line (forced here: it needs no RCCL) leaves the exit code alone"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(MPPI_BENCH_BACKEND="gloo", MPPI_BENCH_MAILBOX_AB="force", MPPI_BENCH_SHIPPED="0")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "5"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "5", "--full"],
                          capture_output=True, text=True, timeout=1200, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = out.stdout.strip().splitlines()
@@ -139,7 +160,7 @@ def test_bench_two_ranks_exchange_through_the_library_mailbox():
     the 8-GPU node the inboxes are peers over xGMI."""
     env = dict(os.environ, MPPI_BENCH_BACKEND="gloo", MPPI_BENCH_EXCHANGE="mailbox", MPPI_BENCH_SECOND="0")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                          "--master-port", "29617", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "100", "--warmup", "10"],
+                          "--master-port", "29617", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "100", "--warmup", "10", "--full"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = out.stdout.strip().splitlines()
@@ -160,7 +181,7 @@ def test_bench_a_rank_that_refuses_the_mailbox_sends_every_rank_to_the_all_gathe
     env = dict(os.environ, MPPI_BENCH_BACKEND="gloo", MPPI_BENCH_EXCHANGE="mailbox", MPPI_BENCH_SECOND="0", MPPI_BENCH_SHIPPED="0",
                MPPI_BENCH_TEST_REFUSE_RANK="1")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                          "--master-port", "29619", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "50", "--warmup", "5"],
+                          "--master-port", "29619", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "50", "--warmup", "5", "--full"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads(out.stdout.strip().splitlines()[-1])

@@ -461,7 +461,7 @@ def watch():
 t = threading.Thread(target=watch, daemon=True); t.start()
 ctx = C.c_void_p()
 rc = lib.mppi_create(C.byref(m), C.byref(cfg), 0, C.byref(ctx))
-print("RC", rc, lib.mppi_last_error().decode()[:300].replace("\\n", " "))
+print("RC", rc, lib.mppi_last_error().decode().replace("\\n", " "))
 print("SEEN", [s[:40] for s in seen])
 '''
     urdf4, actor4 = str(tmp_path / "b4.urdf"), str(tmp_path / "arm4.yaml")

@@ -12,8 +12,8 @@ if [[ $WHAT == *tests* ]]; then
   tail -25 $OUT/gpu_tests.log
 fi
 if [[ $WHAT == *bench* ]]; then
-  timeout 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
-  timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_driver_cmd.json 2>> $OUT/bench.err
+  timeout 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+  timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_driver_cmd.json 2>> $OUT/bench.err
   python - $OUT/bench.json $OUT/bench_driver_cmd.json <<'PY'
 import json, sys
 for f in sys.argv[1:]:
@@ -31,8 +31,8 @@ if [[ $WHAT == *facade* ]]; then
   head -40 $OUT/facade_profile.txt; tail -5 $OUT/facade_profile.err
 fi
 if [[ $WHAT == *benchall* ]]; then
-  for w in point_reach boxer_push panda_pick; do timeout 300 python bench.py --no-cpu-baseline --workload $w > $OUT/bench_$w.json 2>> $OUT/bench.err; done
-  timeout 600 python bench.py --no-cpu-baseline --workload panda_pick --k-total 65536 --steps 40 --warmup 5 > $OUT/bench_panda_pick_65536.json 2>> $OUT/bench.err
+  for w in point_reach boxer_push panda_pick; do timeout 300 python bench.py --full --no-cpu-baseline --workload $w > $OUT/bench_$w.json 2>> $OUT/bench.err; done
+  timeout 600 python bench.py --full --no-cpu-baseline --workload panda_pick --k-total 65536 --steps 40 --warmup 5 > $OUT/bench_panda_pick_65536.json 2>> $OUT/bench.err
 fi
 if [[ $WHAT == *prof* ]]; then
   WORKLOAD=panda_reach STEPS=300 bash tools/profile_bench.sh ${TAG} > $OUT/prof_reach.log 2>&1

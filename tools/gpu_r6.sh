@@ -16,13 +16,13 @@ if [[ $WHAT == *tests* ]]; then
   grep -E "passed|failed|FAILED|Error|rc=" $OUT/gpu_tests.log | tail -40
 fi
 if [[ $WHAT == *bench* ]]; then
-  timeout 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
-  timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_driver_cmd.json 2>> $OUT/bench.err
+  timeout 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+  timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_driver_cmd.json 2>> $OUT/bench.err
   tail -5 $OUT/bench.err
 fi
 if [[ $WHAT == *benchall* ]]; then
-  for w in point_reach boxer_push panda_pick; do timeout 300 python bench.py --no-cpu-baseline --workload $w > $OUT/bench_$w.json 2>> $OUT/bench.err; done
-  timeout 600 python bench.py --no-cpu-baseline --workload panda_pick --k-total 65536 --steps 40 --warmup 5 > $OUT/bench_panda_pick_65536.json 2>> $OUT/bench.err
+  for w in point_reach boxer_push panda_pick; do timeout 300 python bench.py --full --no-cpu-baseline --workload $w > $OUT/bench_$w.json 2>> $OUT/bench.err; done
+  timeout 600 python bench.py --full --no-cpu-baseline --workload panda_pick --k-total 65536 --steps 40 --warmup 5 > $OUT/bench_panda_pick_65536.json 2>> $OUT/bench.err
 fi
 if [[ $WHAT == *ab* ]]; then
   timeout 600 python tools/exp/ab_time.py ${AB_ARGS:-} > $OUT/ab_time.txt 2>&1; cat $OUT/ab_time.txt | tail -30

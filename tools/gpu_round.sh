@@ -8,14 +8,14 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/$TAG
 mkdir -p $OUT
 cd $REPO
-B="python bench.py --no-cpu-baseline"
+B="python bench.py --full --no-cpu-baseline"
 if [[ $WHAT == *tests* ]]; then
   timeout 1500 python -m pytest tests -m gpu -q -s --durations=15 > $OUT/gpu_tests.log 2>&1; echo "pytest rc=$?" >> $OUT/gpu_tests.log
   tail -5 $OUT/gpu_tests.log
 fi
 if [[ $WHAT == *bench* ]]; then
-  timeout 300 python bench.py > $OUT/bench.json 2> $OUT/bench.err
-  timeout 300 python bench.py --steps 2000 --warmup 200 --no-cpu-baseline > $OUT/bench_2000.json 2>> $OUT/bench.err
+  timeout 300 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+  timeout 300 python bench.py --full --steps 2000 --warmup 200 --no-cpu-baseline > $OUT/bench_2000.json 2>> $OUT/bench.err
   for w in point_reach boxer_push panda_pick; do timeout 300 $B --workload $w > $OUT/bench_$w.json 2>> $OUT/bench.err; done
   timeout 600 $B --workload panda_pick --k-total 65536 --steps 40 --warmup 5 > $OUT/bench_panda_pick_65536.json 2>> $OUT/bench.err
 fi
