@@ -275,7 +275,7 @@ bool owned_and_private(const std::string &path, bool is_dir, std::string &why) {
 }
 // FNV-1a over the kernel headers and the ABI header: a plugin is only ever loaded next to the sources it was built from
 bool source_key(const std::string &dir, uint64_t &key, std::string &err) {
-    const char *files[] = {"mppi_kernels.hpp", "mppi_device.hpp", "mppi_quad.hpp", "mppi_oct.hpp", "mppi_scene.hpp", "mppi_scene_quad.hpp", "mppi_scene_oct.hpp",
+    const char *files[] = {"mppi_kernels.hpp", "mppi_device.hpp", "mppi_quad.hpp", "mppi_oct.hpp", "mppi_oct_pair.hpp", "mppi_scene.hpp", "mppi_scene_quad.hpp", "mppi_scene_oct.hpp",
                            "mppi_pack.hpp", "topologies.inc", "../../include/mppi_hip.h"};
     uint64_t h = 1469598103934665603ull;
     for (const char *f : files) {
@@ -563,6 +563,14 @@ int mppi_create(const mppi_model_t *model, const mppi_config_t *cfg, int device,
             const bool oct = c->quad && !(mode && std::string(mode) == "quad") && cfg->num_samples >= 8 && oct_fits;
             c->lanes_per_sample = c->quad ? (oct ? 8 : 4) : 1;
             c->launch_rollout = c->quad ? (oct ? e->rollout_oct : e->rollout_quad) : e->rollout;
+            // ... and with two HELPER wavefronts per workgroup of 16 samples (mppi_oct_pair.hpp: controls, cost and output leave the
+            // owners' instruction stream).  Four wavefronts of more than 256 registers take the four SIMDs of a CU, so it is chosen
+            // while every workgroup gets a CU of its own (K <= 16 x CUs: 4096 on the MI355X) and the horizon fits its control
+            // table; MPPI_ROLLOUT=oct keeps the octet kernel without helpers (the A/B partner), =oct-pair lifts the CU bound.
+            const bool pair_forced = mode && std::string(mode) == "oct-pair";
+            c->pair_free = oct && e->rollout_oct_pair != nullptr && !(mode && std::string(mode) == "oct") && cfg->horizon <= kPairTableH &&
+                           ((cfg->num_samples + 15) / 16 <= cus || pair_forced);
+            if (c->pair_free) c->launch_rollout = e->rollout_oct_pair;
             c->launch_rollout_lane = e->rollout;  // cost programs on contact-free scenes run on the one-lane kernel
             if (c->quad) {
                 c->launch_rollout_traj = oct ? e->rollout_oct_traj : e->rollout_traj;
@@ -1385,7 +1393,7 @@ int mppi_kernel_ms(mppi_ctx_t *c, int which, float *ms) {
 }
 int mppi_kernel_info(mppi_ctx_t *c, char *buf, int buflen) {
     CTX_TRY(c);
-    std::snprintf(buf, buflen, "topology=%s rollout=%s K=%d H=%d nu=%d waves=%d block=%d bytes_alg=%zu", c->topo.c_str(), c->scene ? (c->helper_wave ? "scene-oct-pair" : (c->lanes_per_sample == 8 ? "scene-oct" : (c->quad ? "scene-quad" : "scene"))) : (c->quad ? (c->lanes_per_sample == 8 ? "oct" : "quad") : "lane"), c->K, c->H, c->nu, c->quad ? c->n_quads * ((c->lanes_per_sample == 8 && !c->scene) ? 2 : 1) : c->n_waves, kWave,
+    std::snprintf(buf, buflen, "topology=%s rollout=%s K=%d H=%d nu=%d waves=%d block=%d bytes_alg=%zu", c->topo.c_str(), c->scene ? (c->helper_wave ? "scene-oct-pair" : (c->lanes_per_sample == 8 ? "scene-oct" : (c->quad ? "scene-quad" : "scene"))) : (c->quad ? (c->lanes_per_sample == 8 ? (c->pair_free ? "oct-pair" : "oct") : "quad") : "lane"), c->K, c->H, c->nu, c->quad ? c->n_quads * ((c->lanes_per_sample == 8 && !c->scene) ? (c->pair_free ? 4 : 2) : 1) : c->n_waves, kWave,
                   (size_t)4 * (3 * (size_t)c->K * c->HN + 2 * (size_t)c->K + c->HN));
     return MPPI_OK;
 }

@@ -29,6 +29,7 @@
 #include "mppi_scene.hpp"
 #include "mppi_quad.hpp"
 #include "mppi_oct.hpp"
+#include "mppi_oct_pair.hpp"
 #include "mppi_scene_quad.hpp"
 #include "mppi_scene_oct.hpp"
 
@@ -39,6 +40,7 @@ struct mppi_ctx;
 namespace {
 
 constexpr int kWave = 64;
+constexpr int kPairTableH = 32;  // horizon steps the control table of k_rollout_oct_pair holds (mppi_oct_pair.hpp kPairMaxH)
 
 // ------------------------------------------------------------------------------ wave helpers
 __device__ __forceinline__ float wave_sum(float v) {
@@ -482,6 +484,167 @@ __global__ __launch_bounds__(LAY == 8 ? 2 * kWave : kWave) void k_rollout_quad(c
         fold_after_record(*(CCfg *)cfg, partials, fold_ctr, fold_out);
     }
     if (wave_clk != nullptr && threadIdx.x == 0) {  // instrumentation (mppi_set_wave_clock): this wavefront's residency
+        wave_clk[2 * chunk] = clk0;
+        wave_clk[2 * chunk + 1] = wall_clock64();
+    }
+#endif
+}
+
+#if defined(__HIP_DEVICE_COMPILE__)
+// The record of a workgroup of the kernel with helper wavefronts (k_rollout_oct_pair: wavefronts 0, 1 own, 2, 3 help): what
+// oct_record2 writes, value for value, from the helpers' costs (they hold S) and from the control table in LDS instead of the du
+// rows in memory - du = u - U[t] is the subtraction apply_controls_q stored, redone on the same operands - so that neither the
+// fence nor the round trip to L2 stands in front of the kernel's end.  All 256 threads sum rows.
+template <class T>
+__device__ __forceinline__ void oct_record_pair(CCfg &cfg, LStep &sc, float s, bool live_leader, bool helper, const MPPI_LDS_AS float *utab, int k0,
+                                                float *__restrict__ rec, int slot) {
+    constexpr int NT = 4 * kWave, SPG = 16, kStride = PairLayout<T>::kStride, kRow = PairLayout<T>::kRow;
+    __shared__ float s_w[SPG], s_b[2], s_e[2];
+    const int K = cfg.K, nu = cfg.nu, HN = cfg.H * nu;
+    const int lane = threadIdx.x & (kWave - 1), wv = (threadIdx.x >> 6) & 1;
+    const bool fin = live_leader && isfinite(s);
+    const float bw = wave_min(fin ? s : INFINITY);
+    if (helper && lane == 0) s_b[wv] = bw;
+    MPPI_BARRIER(12);
+    const float beta = fminf(s_b[0], s_b[1]);
+    const float w = fin ? __expf(-(s - beta) * cfg.inv_lambda) : 0.f;
+    const float ew = wave_sum(w);
+    if (helper && lane == 0) s_e[wv] = ew;
+    if (helper && (lane & 3) == 0 && ((lane >> 3) & 1) == 0) s_w[wv * 8 + slot] = w;  // the leader lane of every slot (w = 0: no such sample)
+    MPPI_BARRIER(13);
+    if (threadIdx.x == 0) {
+        rec[0] = beta;
+        rec[1] = s_e[0] + s_e[1];
+    }
+    const int nlive = K - k0 < SPG ? K - k0 : SPG;
+    if (nlive == SPG && (K & 3) == 0) {
+        // (oct_record2's aligned path statement for statement - its 128 threads, its two trips - so that the compiler contracts
+        // the products and sums of a row alike: the order of a*b + c*d inside a fused multiply-add is its choice per trip)
+        constexpr int kTrips = 2, NR = 2 * kWave;
+        if (threadIdx.x >= NR) return;
+        float wq[SPG];
+#pragma unroll
+        for (int q = 0; q < SPG; q++) wq[q] = s_w[q];
+        for (int j0 = threadIdx.x; j0 < HN; j0 += kTrips * NR) {
+            float4 v[kTrips][SPG / 4];
+#pragma unroll
+            for (int t = 0; t < kTrips; t++) {
+                const int j = j0 + t * NR;
+                if (j < HN) {
+                    const int ts = j / nu, c = j - ts * nu;
+                    const float Ut = sc.Urow[ts].v[c];
+                    const MPPI_LDS_AS float *col = utab + ts * kRow + c;
+#pragma unroll
+                    for (int q = 0; q < SPG / 4; q++)
+                        v[t][q] = make_float4(col[(4 * q) * kStride] - Ut, col[(4 * q + 1) * kStride] - Ut, col[(4 * q + 2) * kStride] - Ut, col[(4 * q + 3) * kStride] - Ut);
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < kTrips; t++) {
+                const int j = j0 + t * NR;
+                if (j < HN) {
+                    float acc = 0.f;
+#pragma unroll
+                    for (int q = 0; q < SPG / 4; q++)
+                        acc += v[t][q].x * wq[4 * q] + v[t][q].y * wq[4 * q + 1] + v[t][q].z * wq[4 * q + 2] + v[t][q].w * wq[4 * q + 3];
+                    rec[2 + j] = acc;
+                }
+            }
+        }
+        return;
+    }
+    for (int j = threadIdx.x; j < HN; j += NT) {
+        const int t = j / nu, c = j - t * nu;
+        const float Ut = sc.Urow[t].v[c];
+        const MPPI_LDS_AS float *col = utab + t * kRow + c;
+        float acc = 0.f;
+        for (int q = 0; q < nlive; q++) acc += (col[q * kStride] - Ut) * s_w[q];
+        rec[2 + j] = acc;
+    }
+}
+
+#endif
+
+// The contact-free octet rollout with helper wavefronts (mppi_oct_pair.hpp): 256 threads for 16 consecutive samples - wavefronts
+// 0 and 1 own eight samples each exactly as in k_rollout_quad<T, false, 8>, wavefronts 2 and 3 form their controls and costs.
+// Four wavefronts of 257 registers: one workgroup per CU, so the host selects it while the grid fits the device's CUs.
+template <class T>
+__global__ __launch_bounds__(4 * kWave) void k_rollout_oct_pair(const DevModel *__restrict__ m, const DevCfg *__restrict__ cfg,
+                                                                const DevCost *__restrict__ cost, const float *__restrict__ x0_dof,
+                                                                const float *__restrict__ x0_root, const float *__restrict__ U,
+                                                                const float *__restrict__ eps, const float *__restrict__ prior,
+                                                                float *__restrict__ du, float *__restrict__ S, float *__restrict__ viz,
+                                                                float *__restrict__ partials, unsigned *__restrict__ fold_ctr, float *__restrict__ fold_out,
+                                                                unsigned long long *__restrict__ wave_clk) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const unsigned long long clk0 = wave_clk != nullptr ? wall_clock64() : 0ull;
+    // ONE wavefront per SIMD, whatever the register count of this build: the owners must not share a SIMD with anybody (the
+    // octet kernel has that from its 256 + 1 registers).  Naming a high AGPR as clobbered puts the wavefront's allocation of
+    // the unified register file above one half of it; no instruction is issued for it.
+    asm volatile("; one wavefront per SIMD" ::: "a31");
+    constexpr int NT = 4 * kWave;
+    // staging as in k_rollout_quad: the robot model, the step constants, the linear lanes' copy of the bodies
+    constexpr int kModelBytes = (int)((offsetof(DevModel, fr) + 15) / 16 * 16);
+    __shared__ __attribute__((aligned(64))) uint4 s_model[kModelBytes / 16];
+    constexpr int kModelTrips = (kModelBytes / 16 + NT - 1) / NT;
+    uint4 mv[kModelTrips];
+#pragma unroll
+    for (int it = 0; it < kModelTrips; it++) {
+        const int i = (int)threadIdx.x + it * NT;
+        mv[it] = reinterpret_cast<const uint4 *>(m)[i < kModelBytes / 16 ? i : 0];
+    }
+    __shared__ __attribute__((aligned(64))) float s_step[sizeof(StepConsts) / sizeof(float)];
+    {
+        const int n = step_const_count(*(CCfg *)cfg);
+        for (int j = threadIdx.x; j < n; j += NT) s_step[j] = step_const_entry(*(CCfg *)cfg, *(CCost *)cost, x0_root, U, j);
+    }
+#pragma unroll
+    for (int it = 0; it < kModelTrips; it++) {
+        const int i = (int)threadIdx.x + it * NT;
+        if (i < kModelBytes / 16) s_model[i] = mv[it];
+    }
+    __shared__ __attribute__((aligned(256))) uint4 s_lin_raw[oct_lin_raw_bytes(T::NB) / 16];
+    LModel &lm = *(LModel *)s_model;
+    LStep &sc = *(LStep *)s_step;
+    MPPI_LDS_AS DevBody *s_lin = oct_lin_place((MPPI_LDS_AS void *)s_lin_raw, &lm.b[0]);
+    if ((int)threadIdx.x < T::NB) {
+        DevBody b = ((const DevModel *)m)->b[threadIdx.x];
+        b.k1 = oct_lin_view(b.k1);
+        s_lin[threadIdx.x] = b;
+    }
+    static_assert(kPairTableH == kPairMaxH, "the host selects by the table the kernel allocates");
+    // the control table and the hand-over ring (mppi_oct_pair.hpp)
+    __shared__ __attribute__((aligned(16))) float s_utab[PairLayout<T>::kTable];
+    __shared__ f32x4 s_xa[2 * 2 * kWave], s_xb[2 * 2 * kWave];
+    __syncthreads();
+    const int nb = gridDim.x;   // XCD-aware chunk mapping as in k_rollout_quad
+    const int chunk = (nb % 16 == 0) ? (int)(blockIdx.x % 8) * (nb / 8) + (int)(blockIdx.x / 8) : (int)blockIdx.x;
+    const int wave = (int)(threadIdx.x >> 6), own = wave & 1;   // helper wavefront 2 + w serves owner w
+    const bool helper = wave >= 2;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int k = chunk * 16 + own * 8 + oct_slot();
+    const int K = cfg->K;
+    const bool live = k < K;            // the lanes of a sample share k
+    const int ke = live ? k : K - 1;    // (samples that do not exist: the last one again - every wavefront keeps every barrier)
+    const bool leader = (threadIdx.x & 3) == 0 && oct_half() == 0;
+    const bool want_viz = cfg->want_rollouts && viz != nullptr;
+    MPPI_LDS_AS float *utab = (MPPI_LDS_AS float *)s_utab;
+    MPPI_LDS_AS float *urow = utab + (own * 8 + oct_slot()) * PairLayout<T>::kStride;
+    LF4 *xa = (LF4 *)s_xa + own * kWave + lane, *xb = (LF4 *)s_xb + own * kWave + lane;
+    float s = INFINITY;
+    if (!helper) {
+        // one wave-uniform branch picks the instruction stream specialised for an all-revolute tree
+        const OctAba ab{oct_bodies(&lm.b[0], s_lin), oct_lane()};
+        if (((CModel *)m)->all_revolute) pair_owner<T, 0>(lm, *(CCfg *)cfg, *(CCost *)cost, x0_dof, x0_root, urow, xa, xb, 2 * kWave, want_viz, ab);
+        else pair_owner<T, -1>(lm, *(CCfg *)cfg, *(CCost *)cost, x0_dof, x0_root, urow, xa, xb, 2 * kWave, want_viz, ab);
+    } else {
+        s = pair_helper<T>(lm, *(CCfg *)cfg, *(CCost *)cost, sc, eps, prior, du, viz, ke, quad_row(), urow, xa, xb, 2 * kWave);
+        if (!live) s = INFINITY;
+        if (live && leader) S[k] = s;
+    }
+    oct_record_pair<T>(*(CCfg *)cfg, sc, s, helper && live && leader, helper, utab, chunk * 16, partials + (size_t)chunk * (2 + cfg->H * cfg->nu), oct_slot());
+    fold_after_record<4>(*(CCfg *)cfg, partials, fold_ctr, fold_out);
+    if (wave_clk != nullptr && threadIdx.x == 0) {  // instrumentation (mppi_set_wave_clock): this workgroup's residency
         wave_clk[2 * chunk] = clk0;
         wave_clk[2 * chunk + 1] = wall_clock64();
     }
@@ -1649,6 +1812,7 @@ struct mppi_ctx {
     void (*launch_rollout_traj)(mppi_ctx *) = nullptr;
     void (*launch_materialise_traj)(mppi_ctx *, float *, float *, float *, float *) = nullptr;
     void (*launch_materialise_traj_link)(mppi_ctx *, int, float *) = nullptr;  // one robot link of all H*K env-steps (contact-free scenes)
+    bool pair_free = false;    // contact-free octet rollout with helper wavefronts (k_rollout_oct_pair)
     bool helper_wave = false;  // octet rollout kernel with a second wavefront per sample group for half of the contact pairs
     int n_partials = 0;   // records currently held by d_partials
     bool quad = false;
@@ -1717,6 +1881,7 @@ struct TopoEntry {
     void (*rollout_quad)(mppi_ctx *);
     void (*rollout_oct)(mppi_ctx *);        // contact-free scenes, octet layout of the solve (8 lanes per sample)
     void (*rollout_oct_traj)(mppi_ctx *);
+    void (*rollout_oct_pair)(mppi_ctx *);   // octet layout + two helper wavefronts per workgroup (mppi_oct_pair.hpp)
     void (*rollout_scene)(mppi_ctx *);
     void (*rollout_scene_quad)(mppi_ctx *);
     void (*rollout_scene_oct)(mppi_ctx *);  // 8 lanes per sample
@@ -1896,6 +2061,13 @@ void launch_rollout_oct_t(mppi_ctx *c) {
                        c->d_U, c->eps_in, c->has_prior ? c->d_prior : nullptr, c->d_du, c->d_S, c->cfg.want_rollouts ? c->d_viz : nullptr, c->d_partials,
                        c->fold ? c->d_fold_ctr : nullptr, c->fold_out, c->wave_clk_on ? c->d_wave_clk : nullptr);
 }
+// ... and with two helper wavefronts per workgroup (controls, cost and output off the owners' instruction stream)
+template <class T>
+void launch_rollout_oct_pair_t(mppi_ctx *c) {
+    hipLaunchKernelGGL(k_rollout_oct_pair<T>, dim3(c->n_quads), dim3(4 * kWave), 0, c->stream, c->d_model, c->d_cfg, c->d_cost, c->d_x0_dof, c->d_x0_root,
+                       c->d_U, c->eps_in, c->has_prior ? c->d_prior : nullptr, c->d_du, c->d_S, c->cfg.want_rollouts ? c->d_viz : nullptr, c->d_partials,
+                       c->fold ? c->d_fold_ctr : nullptr, c->fold_out, c->wave_clk_on ? c->d_wave_clk : nullptr);
+}
 template <class T>
 void launch_rollout_oct_traj_t(mppi_ctx *c) {
     hipLaunchKernelGGL((k_rollout_quad<T, true, 8>), dim3(c->n_quads), dim3(2 * kWave), 0, c->stream, c->d_model, c->d_cfg, c->d_cost_none, c->d_x0_dof, c->d_x0_root,
@@ -1968,6 +2140,7 @@ void fill_topo_entry_free(TopoEntry &e) {
     e.rollout_quad = &launch_rollout_quad_t<T>;
     e.rollout_oct = &launch_rollout_oct_t<T>;
     e.rollout_oct_traj = &launch_rollout_oct_traj_t<T>;
+    e.rollout_oct_pair = &launch_rollout_oct_pair_t<T>;
     e.sim_step = &launch_sim_step_t<T>;
     e.sim_step_quad = &launch_sim_step_quad_t<T>;
     e.rollout_traj = &launch_rollout_traj_t<T>;

@@ -805,20 +805,29 @@ MPPI_HD void quad_body_pose(const QPose<T, JT> &P, int body, QM3 &Rb, QF &pb) {
     }
 }
 
+// world pose of a link (block L of the model) out of the world pose (Rb, pb) of the body that carries it
+template <class LK>
+MPPI_HD void quad_link_from_body(LK &L, const QM3 &Rb, QF pb, QM3 &R, QF &p) {
+    for (int c = 0; c < 3; c++) R.c[c] = Rb.c[0] * L.R[c] + Rb.c[1] * L.R[3 + c] + Rb.c[2] * L.R[6 + c];
+    p = pb + Rb.c[0] * L.p[0] + Rb.c[1] * L.p[1] + Rb.c[2] * L.p[2];
+}
+// world pose of the body that carries link l (wave-uniform choice)
+template <class T, class M, int JT>
+MPPI_HD void quad_link_body_pose(M &m, const QPose<T, JT> &P, int l, QM3 &Rb, QF &pb) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const int body = __builtin_amdgcn_readfirstlane(m.l[l].body);  // (from the LDS copy of the model it arrives in a vector register)
+#else
+    const int body = m.l[l].body;
+#endif
+    quad_body_pose<T, JT, -1, T::NB>(P, body < 0 ? -1 : (body < T::NB ? body : T::NB - 1), Rb, pb);
+}
 // world pose of link l: row r of R (standard) and component r of p
 template <class T, class M, int JT>
 MPPI_HD void quad_link_pose(M &m, const QPose<T, JT> &P, int l, QM3 &R, QF &p) {
-    auto &L = m.l[l];
-#if defined(__HIP_DEVICE_COMPILE__)
-    const int body = __builtin_amdgcn_readfirstlane(L.body);  // (from the LDS copy of the model it arrives in a vector register)
-#else
-    const int body = L.body;
-#endif
     QM3 Rb;
     QF pb;
-    quad_body_pose<T, JT, -1, T::NB>(P, body < 0 ? -1 : (body < T::NB ? body : T::NB - 1), Rb, pb);
-    for (int c = 0; c < 3; c++) R.c[c] = Rb.c[0] * L.R[c] + Rb.c[1] * L.R[3 + c] + Rb.c[2] * L.R[6 + c];
-    p = pb + Rb.c[0] * L.p[0] + Rb.c[1] * L.p[1] + Rb.c[2] * L.p[2];
+    quad_link_body_pose<T>(m, P, l, Rb, pb);
+    quad_link_from_body(m.l[l], Rb, pb, R, p);
 }
 
 // Per-rollout constants of the step loop, staged next to the robot model (LDS on the device).  Through the scalar cache

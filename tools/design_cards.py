@@ -34,12 +34,12 @@ def rocprof_avg(name, needle):
         return None
     with open(path) as f:
         for row in csv.DictReader(f):
-            if needle in row["Name"]:
+            if any(n in row["Name"] for n in needle.split("|")):
                 return float(row["AverageNs"]) / 1e6, int(row["Calls"])
     return None
 
 
-rows = [("panda reach 4096 x 20 (headline)", "bench.json", "", "k_rollout_quad"), ("point reach 1024 x 15", "bench_point_reach.json", None, None),
+rows = [("panda reach 4096 x 20 (headline)", "bench.json", "", "k_rollout_oct_pair|k_rollout_quad"), ("point reach 1024 x 15", "bench_point_reach.json", None, None),
         ("pushing scene 8192 x 25", "bench_boxer_push.json", "_boxer", "k_rollout_scene_quad"), ("gripper scene 8192 x 30", "bench_panda_pick.json", "_pick", "k_rollout_scene_quad"),
         ("gripper scene 65536 x 30, one GPU", "bench_panda_pick_65536.json", None, None)]
 print(f"| workload (`profiles/{tag}_*`) | closed loop | rollout kernel, hipEvents in the timed loop | rocprofv3 average (launches) | HBM per launch, PMC / algorithmic | SQ per wavefront: VALU / SALU / LDS, issuing |")

@@ -34,7 +34,7 @@ for k, v in out.items():
     if "FETCH_SIZE_KB_mean" in v and "WRITE_SIZE_KB_mean" in v:
         v["hbm_traffic_bytes_per_launch"] = int(1024 * (2 * v["FETCH_SIZE_KB_mean"] + v["WRITE_SIZE_KB_mean"]))
 json.dump(out, open(os.path.join(dst, f"{tag}_pmc_summary.json"), "w"), indent=1, sort_keys=True)
-main = out.get("k_rollout_quad") or out.get("k_rollout_scene_quad") or out.get("k_rollout", {})
+main = out.get("k_rollout_oct_pair") or out.get("k_rollout_quad") or out.get("k_rollout_scene_quad") or out.get("k_rollout", {})
 latest_path = os.path.join(dst, "pmc_latest.json")
 latest = json.load(open(latest_path)) if os.path.exists(latest_path) else {}
 if "by_workload" not in latest:

@@ -68,7 +68,7 @@ json.dump(summary, open(os.path.join(src, "sq_summary.json"), "w"), indent=1, so
 dst = os.path.join(ROOT, "profiles")
 if os.path.isdir(dst) and summary["workload"]:
     json.dump(summary, open(os.path.join(dst, f"{tag}_sq_summary.json"), "w"), indent=1, sort_keys=True)
-    main = next((out[k] for k in ("k_rollout_quad", "k_rollout_scene_quad", "k_rollout", "k_rollout_scene") if k in out), None)
+    main = next((out[k] for k in ("k_rollout_oct_pair", "k_rollout_quad", "k_rollout_scene_quad", "k_rollout", "k_rollout_scene") if k in out), None)
     lp = os.path.join(dst, "sq_latest.json")
     latest = json.load(open(lp)) if os.path.exists(lp) else {"by_workload": {}}
     latest["by_workload"][summary["workload"].split(" ")[0]] = {"tag": tag, "K": summary["K"], "H": summary["H"], "k_rollout": main}
