@@ -382,7 +382,11 @@ int mppi_exchange_status(mppi_ctx_t *ctx, int *timed_out);
  * combine + world kernel starts with the reduction to the shard record, the publish and the bounded wait), so that the sharded
  * control iteration has the two launches of the unsharded one; every other context takes the two calls in turn. */
 int mppi_exchange_update_step_world(mppi_ctx_t *planner, mppi_ctx_t *world);
-/* combine n shard records (device, [n][2+H*nu]; NULL = own record), update U, emit action, shift */
+/* combine n shard records (device, [n][2+H*nu]; NULL = own record), update U, emit action, shift.
+ * Non-finite costs: a sample whose cost is NaN or +-Inf has weight 0 in its record (every record routine tests isfinite(S)), a record
+ * without a finite sample has eta = 0 and is skipped by the combine.  If EVERY sample of every record is rejected the combined eta is
+ * 0 and the update adds nothing: beta = +Inf, eta = 0 in mppi_get_weights_stats, the action is the old U[0], the nominal is the old
+ * one shifted by one step with u_init appended - never NaN (tests/test_gpu_rollout_matrix.py). */
 int mppi_update(mppi_ctx_t *ctx, const float *records_dev, int n_records);
 int mppi_get_action(mppi_ctx_t *ctx, float *action_host);     /* [nu]; synchronises the stream        */
 /* The action of the LAST update as soon as the update kernel has published it (the kernel mirrors the action and a

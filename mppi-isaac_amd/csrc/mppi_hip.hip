@@ -1393,7 +1393,9 @@ int mppi_kernel_ms(mppi_ctx_t *c, int which, float *ms) {
 }
 int mppi_kernel_info(mppi_ctx_t *c, char *buf, int buflen) {
     CTX_TRY(c);
-    std::snprintf(buf, buflen, "topology=%s rollout=%s K=%d H=%d nu=%d waves=%d block=%d bytes_alg=%zu", c->topo.c_str(), c->scene ? (c->helper_wave ? "scene-oct-pair" : (c->lanes_per_sample == 8 ? "scene-oct" : (c->quad ? "scene-quad" : "scene"))) : (c->quad ? (c->lanes_per_sample == 8 ? (c->pair_free ? "oct-pair" : "oct") : "quad") : "lane"), c->K, c->H, c->nu, c->quad ? c->n_quads * ((c->lanes_per_sample == 8 && !c->scene) ? (c->pair_free ? 4 : 2) : 1) : c->n_waves, kWave,
+    // (a cost program on a contact-free scene runs on the one-lane kernel whatever was selected at mppi_create: mppi_set_cost)
+    const bool shared = c->quad && !c->prog_lane;
+    std::snprintf(buf, buflen, "topology=%s rollout=%s K=%d H=%d nu=%d waves=%d block=%d bytes_alg=%zu", c->topo.c_str(), c->scene ? (c->helper_wave ? "scene-oct-pair" : (c->lanes_per_sample == 8 ? "scene-oct" : (c->quad ? "scene-quad" : "scene"))) : (shared ? (c->lanes_per_sample == 8 ? (c->pair_free ? "oct-pair" : "oct") : "quad") : "lane"), c->K, c->H, c->nu, shared ? c->n_quads * ((c->lanes_per_sample == 8 && !c->scene) ? (c->pair_free ? 4 : 2) : 1) : c->n_waves, kWave,
                   (size_t)4 * (3 * (size_t)c->K * c->HN + 2 * (size_t)c->K + c->HN));
     return MPPI_OK;
 }

@@ -14,7 +14,7 @@ import pytest
 import torch
 
 from mppiisaac.backend import capi
-from scenes import boxer_push, panda_pick, point_reach
+from scenes import boxer_push, panda_pick, panda_reach, point_reach
 
 pytestmark = pytest.mark.gpu
 CHECK_LIB = os.path.join(os.path.dirname(capi.__file__), "..", "..", "csrc", "libmppi_hip_check.so")
@@ -41,8 +41,12 @@ def costs(lib, m, cfg, cost, dof, root, trajectory=False):
     return S, info.value.decode()
 
 
+# (the contact-free kernel with helper wavefronts, barriers 10 - 13: a workgroup whose second owner has one sample, the last row of
+# its 32-row control table, a horizon shorter than its prefetch pipeline)
 @pytest.mark.parametrize("make,K,H,kernel", [(boxer_push, 1021, 8, "scene-oct-pair"), (boxer_push, 8192, 6, "scene-oct-pair"),
-                                             (panda_pick, 999, 6, "scene-oct"), (point_reach, 77, 5, None)])
+                                             (panda_pick, 999, 6, "scene-oct"), (point_reach, 77, 5, "oct-pair"),
+                                             (panda_reach, 9, 32, "oct-pair"), (panda_reach, 1000, 32, "oct-pair"),
+                                             (point_reach, 77, 2, "oct-pair")])
 def test_check_build_finds_nothing(make, K, H, kernel):
     assert torch.cuda.is_available()
     assert os.path.exists(CHECK_LIB), "libmppi_hip_check.so is missing: __graft_entry__.build() builds it next to the product library"

@@ -103,7 +103,9 @@ def test_unseen_branched_urdf_is_compiled_built_and_planned_on(tmp_path, monkeyp
     reach.kind = capi.COST_PANDA_REACH
     reach.link[0], reach.actor[0] = sim.scene.rigid_body_index("arm5", "tool"), sim.scene.actor_index("goal")
     reach.w[0], reach.w[1] = 1.0, 0.3
-    for cost, kernel in ((reach, "rollout=oct"), (program(sim, "l4", "goal"), "rollout=oct")):   # (a program on a contact-free scene: the plugin's one-lane kernel)
+    # exact kernel names (trailing blank): the in-line kind on the plugin's octet kernel with helper wavefronts, a program on a
+    # contact-free scene on the plugin's one-lane kernel
+    for cost, kernel in ((reach, "rollout=oct-pair "), (program(sim, "l4", "goal"), "rollout=lane ")):
         capi.check(lib, lib.mppi_set_cost(sim._ctx, C.byref(cost)))
         capi.check(lib, lib.mppi_kernel_info(sim._ctx, kinfo, 256))
         assert kernel in kinfo.value.decode(), kinfo.value
