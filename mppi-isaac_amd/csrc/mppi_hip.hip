@@ -95,10 +95,10 @@ int create_buffers(mppi_ctx *c, const mppi_config_t *cfg) {
     c->n = c->hm.nb; c->A = c->hm.n_actors; c->B = c->hm.n_rb; c->K = cfg->num_samples; c->H = cfg->horizon; c->nu = cfg->nu;
     c->HN = c->H * c->nu; c->RF = 2 + c->HN; c->n_waves = (c->K + kWave - 1) / kWave;
     {
-        // samples per workgroup (= per record) of the rollout kernel that shares lanes: 16, contact scenes in the octet layout 8
-        // (the contact-free octet kernel runs two wavefronts of eight samples per workgroup)
-        const int spw = (c->lanes_per_sample == 8 && c->scene) ? 8 : 16;
-        c->n_quads = (c->K + spw - 1) / spw;
+        // records of the shared-lane rollout kernel: one per workgroup (RolloutKind); a one-lane context keeps room for the
+        // records of 16 samples that k_reduce_quad writes
+        const int spg = c->shared_lanes() ? c->kind().samples_per_group : 16;
+        c->n_quads = (c->K + spg - 1) / spg;
     }
     const size_t K = c->K;
     ALLOC_TRY(c->d_model, sizeof(DevModel));
@@ -515,28 +515,28 @@ int mppi_create(const mppi_model_t *model, const mppi_config_t *cfg, int device,
             c->lds_bytes_table = sizeof(unsigned) * (size_t)scene_table_dwords(c->hm.n_shapes, c->hm.n_pairs);
             // rollouts: 4 lanes per sample (contact points dealt over the quad) unless MPPI_ROLLOUT=lane
             const char *mode = std::getenv("MPPI_ROLLOUT");
-            c->quad = !(mode && std::string(mode) == "lane");
+            bool quad = !(mode && std::string(mode) == "lane");
             // several moving-base robots in one env (ABI 7: one floating base per tree): the one-lane kernels carry them - the
             // shared-lane kernels keep ONE base (conf/mppi/multi-jackal.yaml asks for 100 samples: two wavefronts either way)
-            if (c->hm.n_bases > 1) c->quad = false;
+            if (c->hm.n_bases > 1) quad = false;
             // contact scenes: 8 lanes per sample (contact work dealt over an octet, K/8 wavefronts) unless MPPI_ROLLOUT=quad
             // (4 lanes per sample, the round-1 kernel) or =lane; one-sample contexts (the K = 1 world) keep the quad
-            const bool oct = c->quad && !(mode && std::string(mode) == "quad") && cfg->num_samples >= 8;
-            c->lanes_per_sample = !c->quad ? 1 : (oct ? 8 : 4);
-            c->launch_rollout = c->quad ? (oct ? e->rollout_scene_oct : e->rollout_scene_quad) : e->rollout_scene;
+            const bool oct = quad && !(mode && std::string(mode) == "quad") && cfg->num_samples >= 8;
+            c->launch_rollout = quad ? (oct ? e->rollout_scene_oct : e->rollout_scene_quad) : e->rollout_scene;
             // short trees: the octet kernel with a helper wavefront per sample group (kSplitOctPair) unless MPPI_ROLLOUT=oct
             // (its dead-pair masks are two words, mppi_scene.hpp: a larger candidate list goes to the one-wavefront octet kernel)
             // (... and a scene with a light body's pairs - implicit on both bodies, mppi_scene.hpp "light bodies" - as well: the free
             // actors are solved AFTER the robot there, not next to it)
-            c->helper_wave = oct && e->rollout_scene_pair != nullptr && !(mode && std::string(mode) == "oct") && c->hm.n_pairs <= kPairKernelMaxPairs &&
-                             c->hm.n_light_pairs == 0;
-            if (c->helper_wave) c->launch_rollout = e->rollout_scene_pair;
+            const bool helper_wave = oct && e->rollout_scene_pair != nullptr && !(mode && std::string(mode) == "oct") && c->hm.n_pairs <= kPairKernelMaxPairs &&
+                                     c->hm.n_light_pairs == 0;
+            if (helper_wave) c->launch_rollout = e->rollout_scene_pair;
+            c->rollout = helper_wave ? kSceneOctPair : (oct ? kSceneOct : (quad ? kSceneQuad : kScene));
             if (oct) {  // (whole-horizon trajectories for host-side costs: the octet kernel)
                 c->launch_rollout_traj = e->rollout_scene_traj;
                 c->launch_materialise_traj = e->materialise_scene_traj;
             }
-            c->launch_sim_step = c->quad ? e->sim_step_scene_quad : e->sim_step_scene;  // (the K = 1 world included: one quad)
-            c->step_feeds_back = c->quad;
+            c->launch_sim_step = quad ? e->sim_step_scene_quad : e->sim_step_scene;  // (the K = 1 world included: one quad)
+            c->step_feeds_back = quad;
             c->launch_materialise = e->materialise_scene;
             // (large scenes - e.g. the 12-DoF mobile manipulator with table and block - do not fit the one-lane kernels' 64 rows
             // per wavefront into 160 KiB: those kernels are then simply not available, MPPI_ROLLOUT=lane is refused below)
@@ -551,7 +551,7 @@ int mppi_create(const mppi_model_t *model, const mppi_config_t *cfg, int device,
             // ... and, by default, with the articulated-body solve in the OCTET layout (mppi_oct.hpp: 8 lanes per sample, angular /
             // linear halves of every spatial quantity in two quads, K/8 wavefronts); MPPI_ROLLOUT=quad keeps 4 lanes per sample
             const char *mode = std::getenv("MPPI_ROLLOUT");
-            c->quad = !(mode && std::string(mode) == "lane");
+            const bool quad = !(mode && std::string(mode) == "lane");
             // The octet kernel needs 257 registers: ONE wavefront per SIMD.  Up to K = 8 x SIMDs (8192 on the MI355X) that is all
             // it ever gets; beyond, its second wavefront per SIMD queues behind the first (measured, profiles/
             // r04h_wave_count_scan_oct.txt: 5.09 us per horizon step at K = 8192, 9.95 at 16384) while the 256-register quad
@@ -560,19 +560,19 @@ int mppi_create(const mppi_model_t *model, const mppi_config_t *cfg, int device,
             (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
             (void)hipGetLastError();
             const bool oct_fits = (cfg->num_samples + 7) / 8 <= 4 * cus || (mode && std::string(mode) == "oct");
-            const bool oct = c->quad && !(mode && std::string(mode) == "quad") && cfg->num_samples >= 8 && oct_fits;
-            c->lanes_per_sample = c->quad ? (oct ? 8 : 4) : 1;
-            c->launch_rollout = c->quad ? (oct ? e->rollout_oct : e->rollout_quad) : e->rollout;
+            const bool oct = quad && !(mode && std::string(mode) == "quad") && cfg->num_samples >= 8 && oct_fits;
+            c->launch_rollout = quad ? (oct ? e->rollout_oct : e->rollout_quad) : e->rollout;
             // ... and with two HELPER wavefronts per workgroup of 16 samples (mppi_oct_pair.hpp: controls, cost and output leave the
             // owners' instruction stream).  Four wavefronts of more than 256 registers take the four SIMDs of a CU, so it is chosen
             // while every workgroup gets a CU of its own (K <= 16 x CUs: 4096 on the MI355X) and the horizon fits its control
             // table; MPPI_ROLLOUT=oct keeps the octet kernel without helpers (the A/B partner), =oct-pair lifts the CU bound.
             const bool pair_forced = mode && std::string(mode) == "oct-pair";
-            c->pair_free = oct && e->rollout_oct_pair != nullptr && !(mode && std::string(mode) == "oct") && cfg->horizon <= kPairTableH &&
-                           ((cfg->num_samples + 15) / 16 <= cus || pair_forced);
-            if (c->pair_free) c->launch_rollout = e->rollout_oct_pair;
+            const bool pair_free = oct && e->rollout_oct_pair != nullptr && !(mode && std::string(mode) == "oct") && cfg->horizon <= kPairTableH &&
+                                   ((cfg->num_samples + 15) / 16 <= cus || pair_forced);
+            if (pair_free) c->launch_rollout = e->rollout_oct_pair;
+            c->rollout = pair_free ? kOctPair : (oct ? kOct : (quad ? kQuad : kLane));
             c->launch_rollout_lane = e->rollout;  // cost programs on contact-free scenes run on the one-lane kernel
-            if (c->quad) {
+            if (quad) {
                 c->launch_rollout_traj = oct ? e->rollout_oct_traj : e->rollout_traj;
                 c->launch_materialise_traj = e->materialise_traj;
                 c->launch_materialise_traj_link = e->materialise_traj_link;
@@ -583,12 +583,12 @@ int mppi_create(const mppi_model_t *model, const mppi_config_t *cfg, int device,
             // the reference's examples waits for this kernel every control iteration); MPPI_WORLD_STEP=lane keeps the one-lane kernel
             const char *ws = std::getenv("MPPI_WORLD_STEP");
             const bool world_quad = cfg->num_samples == 1 && !(ws && std::string(ws) == "lane");
-            c->launch_sim_step = (c->quad && (cfg->num_samples >= 64 || world_quad)) ? e->sim_step_quad : e->sim_step;
+            c->launch_sim_step = (quad && (cfg->num_samples >= 64 || world_quad)) ? e->sim_step_quad : e->sim_step;
             c->launch_materialise = e->materialise;
         }
         break;
     }
-    if (ok && ((c->quad ? 0 : c->lds_bytes) > 160 * 1024 || c->lds_bytes_quad + c->lds_bytes_table + c->lds_bytes_static > 160 * 1024)) {
+    if (ok && ((c->shared_lanes() ? 0 : c->lds_bytes) > 160 * 1024 || c->lds_bytes_quad + c->lds_bytes_table + c->lds_bytes_static > 160 * 1024)) {
         delete c;
         return fail(MPPI_EUNSUPPORTED, "contact scene needs more than 160 KiB of LDS per workgroup (dynamic rows + table + the kernels' static __shared__)");
     }
@@ -613,7 +613,7 @@ int mppi_create(const mppi_model_t *model, const mppi_config_t *cfg, int device,
         // scene) win - 445 -> 460 Hz -, the 0.17-ms panda iteration (256 records, 10 us combine) loses 2.6 %: the fold is
         // on for contact scenes and off for the contact-free kernel; MPPI_FOLD=0 / =1 overrides either way.
         const char *f = std::getenv("MPPI_FOLD");
-        c->fold = c->quad && (f ? std::string(f) == "1" : c->scene);
+        c->fold = c->shared_lanes() && (f ? std::string(f) == "1" : c->scene);
     }
     const int rc = create_buffers(c, cfg);
     if (rc != MPPI_OK) {  // (the error text is already set) nothing allocated so far may leak
@@ -683,7 +683,7 @@ int mppi_set_cost(mppi_ctx_t *c, const mppi_cost_t *cost) {
     c->hk = hk;
     // MPPI_COST_PROGRAM on a contact-free scene: the quad kernel's in-line costs stay as they are (its instruction stream is
     // the metric's); the interpreter lives in the one-lane kernel there, and in the scene kernels
-    c->prog_lane = hk.kind == kCostProgram && !c->scene && c->quad && c->launch_rollout_lane != nullptr;
+    c->prog_lane = hk.kind == kCostProgram && !c->scene && c->shared_lanes() && c->launch_rollout_lane != nullptr;
     HIP_TRY(hipMemcpyAsync(c->d_cost, &c->hk, sizeof(DevCost), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->has_cost = true;
@@ -778,7 +778,7 @@ int mppi_rollout(mppi_ctx_t *c) {
         c->n_partials = c->n_quads % 16 == 0 ? kFoldGroups : 1;
         c->recs_cur = c->fold_out;
     } else {
-        c->n_partials = c->quad ? c->n_quads : c->n_waves;
+        c->n_partials = c->shared_lanes() ? c->n_quads : c->n_waves;
         c->recs_cur = c->d_partials;
     }
     return launch_check();
@@ -1342,7 +1342,7 @@ int mppi_set_wave_clock(mppi_ctx_t *c, int on) {
 int mppi_get_wave_clock(mppi_ctx_t *c, uint64_t *start_end_host, int n_wavefronts) {
     CTX_TRY(c);
     if (!c->d_wave_clk || !start_end_host) return fail(MPPI_ESTATE, "mppi_get_wave_clock: not enabled (mppi_set_wave_clock)");
-    const int n = c->quad ? c->n_quads : c->n_waves;
+    const int n = c->shared_lanes() ? c->n_quads : c->n_waves;
     if (n_wavefronts != n) return fail(MPPI_EINVAL, "mppi_get_wave_clock: the rollout kernel runs " + std::to_string(n) + " wavefronts");
     HIP_TRY(hipMemcpyAsync(start_end_host, c->d_wave_clk, sizeof(unsigned long long) * 2 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1394,8 +1394,9 @@ int mppi_kernel_ms(mppi_ctx_t *c, int which, float *ms) {
 int mppi_kernel_info(mppi_ctx_t *c, char *buf, int buflen) {
     CTX_TRY(c);
     // (a cost program on a contact-free scene runs on the one-lane kernel whatever was selected at mppi_create: mppi_set_cost)
-    const bool shared = c->quad && !c->prog_lane;
-    std::snprintf(buf, buflen, "topology=%s rollout=%s K=%d H=%d nu=%d waves=%d block=%d bytes_alg=%zu", c->topo.c_str(), c->scene ? (c->helper_wave ? "scene-oct-pair" : (c->lanes_per_sample == 8 ? "scene-oct" : (c->quad ? "scene-quad" : "scene"))) : (shared ? (c->lanes_per_sample == 8 ? (c->pair_free ? "oct-pair" : "oct") : "quad") : "lane"), c->K, c->H, c->nu, shared ? c->n_quads * ((c->lanes_per_sample == 8 && !c->scene) ? (c->pair_free ? 4 : 2) : 1) : c->n_waves, kWave,
+    const RolloutKind &k = c->prog_lane ? kRolloutKinds[kLane] : c->kind();
+    std::snprintf(buf, buflen, "topology=%s rollout=%s K=%d H=%d nu=%d waves=%d block=%d bytes_alg=%zu", c->topo.c_str(), k.name, c->K, c->H, c->nu,
+                  (c->K + k.samples_per_group - 1) / k.samples_per_group * k.waves_per_group, kWave,
                   (size_t)4 * (3 * (size_t)c->K * c->HN + 2 * (size_t)c->K + c->HN));
     return MPPI_OK;
 }

@@ -6,11 +6,14 @@
 // Launch structure of one control iteration (replaces the reference's Python horizon loop with
 // ~H x (gym set + simulate + fetch + 4 refresh + 15-40 torch kernels), reference
 // mppiisaac/planner/mppi_isaac.py:57-69 / SURVEY.md 3.1):
-//   k_rollout_quad<Topo>  one sample per 4-lane quad, persistent over the whole horizon: perturb/clamp the
-//                         nominal controls, H x substeps articulated-body steps, fused stage cost, discounted
-//                         sum, and - in its tail - the per-wave softmax record (beta, eta, sum w du).
-//                         k_rollout<Topo> (one lane per sample) and k_rollout_scene<Topo> (contact scenes,
-//                         LDS-staged frames) are the other two rollout kernels.
+//   rollout               persistent over the whole horizon: perturb/clamp the nominal controls, H x substeps
+//                         articulated-body steps, fused stage cost, discounted sum, and - in its tail - the softmax record
+//                         (beta, eta, sum w du) of its samples.  One kernel per row of kRolloutKinds (mppi_create selects):
+//                         k_rollout<Topo> (one lane per sample), k_rollout_quad<Topo> (4-lane quad per sample; LAY = 8: 8-lane
+//                         octet), k_rollout_oct_pair<Topo> (octets + helper wavefronts) for contact-free scenes,
+//                         k_rollout_scene<Topo> and k_rollout_scene_quad<Topo, LPS, NW> (LDS-staged frames) for contact scenes.
+//                         The shared-lane kernels share their record row sums (record_rows), their staging (rollout_prologue,
+//                         stage_model, xcd_chunk) and - on the host - one launcher (launch_rollout_kernel).
 //   k_combine[_world]     rescales and sums per-wave / per-GPU records (the same formula joins waves, and
 //                         GPUs after the RCCL all-gather), updates and shifts the nominal U, emits the
 //                         action; the _world variant also steps the K = 1 world and feeds its state back.
@@ -99,7 +102,65 @@ __device__ __forceinline__ void wave_record(CCfg &cfg, float s, bool live, const
     }
 }
 
-// The same record for a wavefront of the kernels whose lanes share samples: SPW samples (chunk * SPW ...), sample s held
+// Row sums of a record, N[j] = sum_q w_q x[j][q] over the SPG samples of a group, written to rec[2 + j]: thread `tid` of NA
+// (aligned path) or NR (ragged path) takes rows tid, tid + NA, ...  Where a row comes from is the row source's business:
+// rows.row(j) gives an object whose four(q) returns the values of samples 4q .. 4q + 3 and whose one(q) that of sample q.
+// A full group (it starts at sample k0 of K) whose rows are 16-byte aligned uses four(q), and the rows of up to kTrips trips of a
+// thread are requested at once (the du rows come back from L2 one round trip per trip of the loop otherwise - three of them in front of the
+// kernel's end for the panda's 140 rows).  The weights come from the caller's own __shared__ array, by reference: DS loads.
+template <int NA, int NR, int kTrips, int SPG, class Rows>
+__device__ __forceinline__ void record_rows(const Rows &rows, const float (&s_w)[SPG], int tid, int HN, int K, int k0, float *__restrict__ rec) {
+    const int nlive = K - k0 < SPG ? K - k0 : SPG;  // samples of this group that exist
+    if (nlive == SPG && (K & 3) == 0) {
+        if (NA < NR && tid >= NA) return;
+        float w[SPG];
+#pragma unroll
+        for (int q = 0; q < SPG; q++) w[q] = s_w[q];
+        for (int j0 = tid; j0 < HN; j0 += kTrips * NA) {
+            float4 v[kTrips][SPG / 4];
+#pragma unroll
+            for (int t = 0; t < kTrips; t++) {
+                const int j = j0 + t * NA;
+                if (j < HN) {
+                    const auto row = rows.row(j);
+#pragma unroll
+                    for (int q = 0; q < SPG / 4; q++) v[t][q] = row.four(q);
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < kTrips; t++) {
+                const int j = j0 + t * NA;
+                if (j < HN) {
+                    float acc = 0.f;
+#pragma unroll
+                    for (int q = 0; q < SPG / 4; q++)
+                        acc += v[t][q].x * w[4 * q] + v[t][q].y * w[4 * q + 1] + v[t][q].z * w[4 * q + 2] + v[t][q].w * w[4 * q + 3];
+                    rec[2 + j] = acc;
+                }
+            }
+        }
+        return;
+    }
+    for (int j = tid; j < HN; j += NR) {
+        const auto row = rows.row(j);
+        float acc = 0.f;
+        for (int q = 0; q < nlive; q++) acc += row.one(q) * s_w[q];
+        rec[2 + j] = acc;
+    }
+}
+// row source: the du rows in memory (sample-minor, the group starts at sample k0)
+struct DuRows {
+    const float *du;
+    int K, k0;
+    struct Row {
+        const float *p;
+        __device__ __forceinline__ float4 four(int q) const { return reinterpret_cast<const float4 *>(p)[q]; }
+        __device__ __forceinline__ float one(int q) const { return p[q]; }
+    };
+    __device__ __forceinline__ Row row(int j) const { return Row{du + (size_t)j * K + k0}; }
+};
+
+// The record of a wavefront of the kernels whose lanes share samples: SPW samples (chunk * SPW ...), sample s held
 // by lanes s*LPS .. s*LPS + LPS-1 (LPS = 64 / SPW lanes per sample: 4 - quad kernels - or 8).  Instead of a 64-lane
 // butterfly per row (6 shuffle steps x H*nu rows), lane l sums rows l, l + 64, ... over the SPW samples itself: the
 // weights are broadcast through LDS, the du values of a row are one contiguous 64- or 32-byte read.
@@ -133,51 +194,13 @@ __device__ __forceinline__ void quad_record(CCfg &cfg, float s, bool live_leader
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     MPPI_BARRIER(5);
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    const int nlive = K - k0 < SPW ? K - k0 : SPW;  // samples of this chunk that exist
-    if (nlive == SPW && (K & 3) == 0) {  // aligned full chunk: 16-byte loads, the rows of up to four trips requested at once
-        // (the du rows come back from L2 one round trip per trip of this loop otherwise - three of them in front of the
-        // kernel's end for the panda's 140 rows)
-        constexpr int kTrips = 4;
-        float w[SPW];
-#pragma unroll
-        for (int q = 0; q < SPW; q++) w[q] = s_w[q];
-        for (int j0 = lane; j0 < HN; j0 += kTrips * kWave) {
-            float4 v[kTrips][SPW / 4];
-#pragma unroll
-            for (int t = 0; t < kTrips; t++) {
-                const int j = j0 + t * kWave;
-                if (j < HN) {
-                    const float4 *row = reinterpret_cast<const float4 *>(du + (size_t)j * K + k0);
-#pragma unroll
-                    for (int q = 0; q < SPW / 4; q++) v[t][q] = row[q];
-                }
-            }
-#pragma unroll
-            for (int t = 0; t < kTrips; t++) {
-                const int j = j0 + t * kWave;
-                if (j < HN) {
-                    float acc = 0.f;
-#pragma unroll
-                    for (int q = 0; q < SPW / 4; q++)
-                        acc += v[t][q].x * w[4 * q] + v[t][q].y * w[4 * q + 1] + v[t][q].z * w[4 * q + 2] + v[t][q].w * w[4 * q + 3];
-                    rec[2 + j] = acc;
-                }
-            }
-        }
-        return;
-    }
-    for (int j = lane; j < HN; j += kWave) {
-        const float *row = du + (size_t)j * K + k0;
-        float acc = 0.f;
-        for (int q = 0; q < nlive; q++) acc += row[q] * s_w[q];
-        rec[2 + j] = acc;
-    }
+    record_rows<kWave, kWave, 4>(DuRows{du, K, k0}, s_w, lane, HN, K, k0, rec);
 }
 
 // The record of a WORKGROUP of two wavefronts that own eight samples each (the octet layout of the contact-free rollout, LAY = 8):
 // 16 consecutive samples -> ONE record, as many records per launch as the quad layout leaves (the combine kernel's time follows
 // their number: 512 records cost it 22.7 us, 256 18.9 us).  beta and eta go through LDS (one barrier each); the rows are summed
-// by the 128 threads as in quad_record<16>.  `slot`: sample slot 0..7 of this lane in its wavefront (oct_slot()).
+// by the 128 threads, both trips of a thread requested at once.  `slot`: sample slot 0..7 of this lane in its wavefront (oct_slot()).
 __device__ __forceinline__ void oct_record2(CCfg &cfg, float s, bool live_leader, const float *__restrict__ du, int k0, float *__restrict__ rec, int slot) {
     constexpr int NT = 2 * kWave, SPG = 16;
     __shared__ float s_w[SPG], s_b[2], s_e[2];
@@ -200,43 +223,7 @@ __device__ __forceinline__ void oct_record2(CCfg &cfg, float s, bool live_leader
         rec[0] = beta;
         rec[1] = s_e[0] + s_e[1];
     }
-    const int nlive = K - k0 < SPG ? K - k0 : SPG;
-    if (nlive == SPG && (K & 3) == 0) {  // aligned full group: 16-byte loads, both trips of a thread requested at once
-        constexpr int kTrips = 2;
-        float wq[SPG];
-#pragma unroll
-        for (int q = 0; q < SPG; q++) wq[q] = s_w[q];
-        for (int j0 = threadIdx.x; j0 < HN; j0 += kTrips * NT) {
-            float4 v[kTrips][SPG / 4];
-#pragma unroll
-            for (int t = 0; t < kTrips; t++) {
-                const int j = j0 + t * NT;
-                if (j < HN) {
-                    const float4 *row = reinterpret_cast<const float4 *>(du + (size_t)j * K + k0);
-#pragma unroll
-                    for (int q = 0; q < SPG / 4; q++) v[t][q] = row[q];
-                }
-            }
-#pragma unroll
-            for (int t = 0; t < kTrips; t++) {
-                const int j = j0 + t * NT;
-                if (j < HN) {
-                    float acc = 0.f;
-#pragma unroll
-                    for (int q = 0; q < SPG / 4; q++)
-                        acc += v[t][q].x * wq[4 * q] + v[t][q].y * wq[4 * q + 1] + v[t][q].z * wq[4 * q + 2] + v[t][q].w * wq[4 * q + 3];
-                    rec[2 + j] = acc;
-                }
-            }
-        }
-        return;
-    }
-    for (int j = threadIdx.x; j < HN; j += NT) {
-        const float *row = du + (size_t)j * K + k0;
-        float acc = 0.f;
-        for (int q = 0; q < nlive; q++) acc += row[q] * s_w[q];
-        rec[2 + j] = acc;
-    }
+    record_rows<NT, NT, 2>(DuRows{du, K, k0}, s_w, threadIdx.x, HN, K, k0, rec);
 }
 
 // Second level of the record tree, still inside the rollout kernel.  The quad kernels deal their chunks so that the
@@ -394,6 +381,74 @@ __global__ __launch_bounds__(kWave) void k_rollout(const DevModel *__restrict__ 
     wave_record(*(CCfg *)cfg, s, live, du, k, partials + (size_t)blockIdx.x * (2 + cfg->H * cfg->nu));
 }
 
+// XCD-aware chunk mapping of the kernels whose workgroups own 16 (or 8) consecutive samples: 16 samples are 64 B of every
+// sample-minor row, i.e. half a 128-B line.  Workgroup b runs on XCD b % 8 and the XCD L2s are private, so with the identity
+// mapping the two halves of each line are fetched by two different L2s (measured: 2x the algorithmic read traffic).  Chunks
+// are therefore dealt so that chunks 2i and 2i+1 land on the same XCD (contact scenes: 128 / (4 SPW) chunks share a line).
+__device__ __forceinline__ int xcd_chunk() {
+    const int nb = gridDim.x;
+    return (nb % 16 == 0) ? (int)(blockIdx.x % 8) * (nb / 8) + (int)(blockIdx.x / 8) : (int)blockIdx.x;
+}
+
+// the first kBytes of the model into LDS by the NT threads of the workgroup, and the barrier behind it
+template <int kBytes, int NT>
+__device__ __forceinline__ void stage_model(uint4 (&s_model)[kBytes / 16], const DevModel *__restrict__ m) {
+    for (int i = threadIdx.x; i < kBytes / 16; i += NT) s_model[i] = reinterpret_cast<const uint4 *>(m)[i];
+    __syncthreads();
+}
+
+#if defined(__HIP_DEVICE_COMPILE__)
+// What the contact-free shared-lane rollout kernels (NT threads per workgroup) stage in LDS before anything else.
+// The robot model (header + body + link blocks, ~4 KB), once per workgroup: constants are then fetched with in-order
+// ds_read_b128 broadcasts into VGPRs - no SMEM round trip (s_waitcnt lgkmcnt(0) on every block), no SGPR spills, no
+// constant-bus moves.  The step loop's own constants (control limits, nominal rows, cost target and weights).  OCT (octet
+// layout): the copy of the bodies' inertia blocks the linear lanes read, inertia tensors and 1/m zero (mppi_oct.hpp
+// oct_lin_view; null otherwise).  Ends with the workgroup's barrier.
+struct RolloutLds {
+    LModel &lm;
+    LStep &sc;
+    MPPI_LDS_AS DevBody *s_lin;
+};
+template <class T, int NT, bool OCT>
+__device__ __forceinline__ RolloutLds rollout_prologue(const DevModel *__restrict__ m, const DevCfg *__restrict__ cfg, const DevCost *__restrict__ cost,
+                                                       const float *__restrict__ x0_root, const float *__restrict__ U) {
+    constexpr int kModelBytes = (int)((offsetof(DevModel, fr) + 15) / 16 * 16);
+    __shared__ __attribute__((aligned(64))) uint4 s_model[kModelBytes / 16];
+    // (the model's loads are all requested first and written to LDS last: their round trip to memory runs under the
+    // staging of the step constants, which has round trips of its own)
+    constexpr int kModelTrips = (kModelBytes / 16 + NT - 1) / NT;
+    uint4 mv[kModelTrips];
+#pragma unroll
+    for (int it = 0; it < kModelTrips; it++) {
+        const int i = (int)threadIdx.x + it * NT;
+        mv[it] = reinterpret_cast<const uint4 *>(m)[i < kModelBytes / 16 ? i : 0];  // (unconditional: the array stays in registers)
+    }
+    __shared__ __attribute__((aligned(64))) float s_step[sizeof(StepConsts) / sizeof(float)];
+    {
+        const int n = step_const_count(*(CCfg *)cfg);
+        for (int j = threadIdx.x; j < n; j += NT) s_step[j] = step_const_entry(*(CCfg *)cfg, *(CCost *)cost, x0_root, U, j);
+    }
+#pragma unroll
+    for (int it = 0; it < kModelTrips; it++) {
+        const int i = (int)threadIdx.x + it * NT;
+        if (i < kModelBytes / 16) s_model[i] = mv[it];
+    }
+    __shared__ __attribute__((aligned(256))) uint4 s_lin_raw[(OCT ? oct_lin_raw_bytes(T::NB) : 16) / 16];
+    LModel &lm = *(LModel *)s_model;
+    MPPI_LDS_AS DevBody *s_lin = nullptr;
+    if constexpr (OCT) {
+        s_lin = oct_lin_place((MPPI_LDS_AS void *)s_lin_raw, &lm.b[0]);   // (bank-disjoint from the model's own blocks)
+        if ((int)threadIdx.x < T::NB) {   // lane i stages body i
+            DevBody b = ((const DevModel *)m)->b[threadIdx.x];
+            b.k1 = oct_lin_view(b.k1);
+            s_lin[threadIdx.x] = b;
+        }
+    }
+    __syncthreads();
+    return RolloutLds{lm, *(LStep *)s_step, s_lin};
+}
+#endif
+
 // Quad-parallel rollout (mppi_quad.hpp): 4 lanes per sample, 16 samples per wavefront.
 // LAY = 8: the OCTET layout of the articulated-body solve (mppi_oct.hpp) - 8 lanes per sample, the angular half of every spatial
 // quantity in one quad and the linear half in the other, 8 samples per wavefront (two per 16-lane row): the same step / rollout
@@ -411,54 +466,9 @@ __global__ __launch_bounds__(LAY == 8 ? 2 * kWave : kWave) void k_rollout_quad(c
                                                         unsigned long long *__restrict__ wave_clk, float *__restrict__ traj = nullptr) {
 #if defined(__HIP_DEVICE_COMPILE__)  // (the host pass sees the 4-float emulation type of mppi_quad.hpp)
     const unsigned long long clk0 = wave_clk != nullptr ? wall_clock64() : 0ull;
-    // Stage the robot model (header + body + link blocks, ~4 KB) in LDS once per wavefront: constants are then
-    // fetched with in-order ds_read_b128 broadcasts into VGPRs - no SMEM round trip (s_waitcnt lgkmcnt(0) on
-    // every block), no SGPR spills, no constant-bus moves.
     // (LAY = 8: a workgroup is TWO wavefronts of eight samples each - 16 consecutive samples, one record, one staged model)
-    constexpr int NT = LAY == 8 ? 2 * kWave : kWave;
-    constexpr int kModelBytes = (int)((offsetof(DevModel, fr) + 15) / 16 * 16);
-    __shared__ __attribute__((aligned(64))) uint4 s_model[kModelBytes / 16];
-    // (the model's loads are all requested first and written to LDS last: their round trip to memory runs under the
-    // staging of the step constants, which has round trips of its own)
-    constexpr int kModelTrips = (kModelBytes / 16 + NT - 1) / NT;
-    uint4 mv[kModelTrips];
-#pragma unroll
-    for (int it = 0; it < kModelTrips; it++) {
-        const int i = (int)threadIdx.x + it * NT;
-        mv[it] = reinterpret_cast<const uint4 *>(m)[i < kModelBytes / 16 ? i : 0];  // (unconditional: the array stays in registers)
-    }
-    // ... and the step loop's own constants (control limits, nominal rows, cost target and weights)
-    __shared__ __attribute__((aligned(64))) float s_step[sizeof(StepConsts) / sizeof(float)];
-    {
-        const int n = step_const_count(*(CCfg *)cfg);
-        for (int j = threadIdx.x; j < n; j += NT) s_step[j] = step_const_entry(*(CCfg *)cfg, *(CCost *)cost, x0_root, U, j);
-    }
-#pragma unroll
-    for (int it = 0; it < kModelTrips; it++) {
-        const int i = (int)threadIdx.x + it * NT;
-        if (i < kModelBytes / 16) s_model[i] = mv[it];
-    }
-    // octet layout: the linear lanes read the bodies' inertia blocks from a copy whose inertia tensors and 1/m are zero
-    // (mppi_oct.hpp oct_lin_view); lane i stages body i
-    __shared__ __attribute__((aligned(256))) uint4 s_lin_raw[(LAY == 8 ? oct_lin_raw_bytes(T::NB) : 16) / 16];
-    LModel &lm = *(LModel *)s_model;
-    LStep &sc = *(LStep *)s_step;
-    MPPI_LDS_AS DevBody *s_lin = nullptr;
-    if constexpr (LAY == 8) {
-        s_lin = oct_lin_place((MPPI_LDS_AS void *)s_lin_raw, &lm.b[0]);   // (bank-disjoint from the model's own blocks)
-        if ((int)threadIdx.x < T::NB) {
-            DevBody b = ((const DevModel *)m)->b[threadIdx.x];
-            b.k1 = oct_lin_view(b.k1);
-            s_lin[threadIdx.x] = b;
-        }
-    }
-    __syncthreads();
-    // XCD-aware chunk mapping: a wavefront owns 16 consecutive samples = 64 B of every sample-minor row, i.e.
-    // half a 128-B line.  Workgroup b runs on XCD b % 8 and the XCD L2s are private, so with the identity
-    // mapping the two halves of each line are fetched by two different L2s (measured: 2x the algorithmic
-    // read traffic).  Chunks are therefore dealt so that chunks 2i and 2i+1 land on the same XCD.
-    const int nb = gridDim.x;
-    const int chunk = (nb % 16 == 0) ? (int)(blockIdx.x % 8) * (nb / 8) + (int)(blockIdx.x / 8) : (int)blockIdx.x;   // 16 samples either way
+    const auto [lm, sc, s_lin] = rollout_prologue<T, (LAY == 8 ? 2 * kWave : kWave), LAY == 8>(m, cfg, cost, x0_root, U);
+    const int chunk = xcd_chunk();   // 16 samples either way
     const int k = chunk * 16 + (LAY == 8 ? (int)(threadIdx.x >> 6) * 8 + oct_slot() : (int)(threadIdx.x >> 2));
     const int lane4 = threadIdx.x & 3;
     const bool live = k < cfg->K;        // the lanes of a sample share k
@@ -491,14 +501,36 @@ __global__ __launch_bounds__(LAY == 8 ? 2 * kWave : kWave) void k_rollout_quad(c
 }
 
 #if defined(__HIP_DEVICE_COMPILE__)
+// row source: the control table of k_rollout_oct_pair in LDS - du = u - U[t] is the subtraction apply_controls_q stored, redone
+// on the same operands
+template <class T>
+struct PairRows {
+    LStep &sc;
+    const MPPI_LDS_AS float *utab;
+    int nu;
+    struct Row {
+        float Ut;
+        const MPPI_LDS_AS float *col;
+        __device__ __forceinline__ float4 four(int q) const {
+            constexpr int kStride = PairLayout<T>::kStride;
+            return make_float4(col[(4 * q) * kStride] - Ut, col[(4 * q + 1) * kStride] - Ut, col[(4 * q + 2) * kStride] - Ut, col[(4 * q + 3) * kStride] - Ut);
+        }
+        __device__ __forceinline__ float one(int q) const { return col[q * PairLayout<T>::kStride] - Ut; }
+    };
+    __device__ __forceinline__ Row row(int j) const {
+        const int t = j / nu, c = j - t * nu;
+        return Row{sc.Urow[t].v[c], utab + t * PairLayout<T>::kRow + c};
+    }
+};
 // The record of a workgroup of the kernel with helper wavefronts (k_rollout_oct_pair: wavefronts 0, 1 own, 2, 3 help): what
 // oct_record2 writes, value for value, from the helpers' costs (they hold S) and from the control table in LDS instead of the du
-// rows in memory - du = u - U[t] is the subtraction apply_controls_q stored, redone on the same operands - so that neither the
-// fence nor the round trip to L2 stands in front of the kernel's end.  All 256 threads sum rows.
+// rows in memory, so that neither the fence nor the round trip to L2 stands in front of the kernel's end.  The aligned path has
+// oct_record2's shape - its 128 threads, its two trips - so the compiler contracts the products and sums of a row alike (the order
+// of a*b + c*d inside a fused multiply-add is its choice per trip); all 256 threads sum ragged rows.
 template <class T>
 __device__ __forceinline__ void oct_record_pair(CCfg &cfg, LStep &sc, float s, bool live_leader, bool helper, const MPPI_LDS_AS float *utab, int k0,
                                                 float *__restrict__ rec, int slot) {
-    constexpr int NT = 4 * kWave, SPG = 16, kStride = PairLayout<T>::kStride, kRow = PairLayout<T>::kRow;
+    constexpr int SPG = 16;
     __shared__ float s_w[SPG], s_b[2], s_e[2];
     const int K = cfg.K, nu = cfg.nu, HN = cfg.H * nu;
     const int lane = threadIdx.x & (kWave - 1), wv = (threadIdx.x >> 6) & 1;
@@ -516,53 +548,8 @@ __device__ __forceinline__ void oct_record_pair(CCfg &cfg, LStep &sc, float s, b
         rec[0] = beta;
         rec[1] = s_e[0] + s_e[1];
     }
-    const int nlive = K - k0 < SPG ? K - k0 : SPG;
-    if (nlive == SPG && (K & 3) == 0) {
-        // (oct_record2's aligned path statement for statement - its 128 threads, its two trips - so that the compiler contracts
-        // the products and sums of a row alike: the order of a*b + c*d inside a fused multiply-add is its choice per trip)
-        constexpr int kTrips = 2, NR = 2 * kWave;
-        if (threadIdx.x >= NR) return;
-        float wq[SPG];
-#pragma unroll
-        for (int q = 0; q < SPG; q++) wq[q] = s_w[q];
-        for (int j0 = threadIdx.x; j0 < HN; j0 += kTrips * NR) {
-            float4 v[kTrips][SPG / 4];
-#pragma unroll
-            for (int t = 0; t < kTrips; t++) {
-                const int j = j0 + t * NR;
-                if (j < HN) {
-                    const int ts = j / nu, c = j - ts * nu;
-                    const float Ut = sc.Urow[ts].v[c];
-                    const MPPI_LDS_AS float *col = utab + ts * kRow + c;
-#pragma unroll
-                    for (int q = 0; q < SPG / 4; q++)
-                        v[t][q] = make_float4(col[(4 * q) * kStride] - Ut, col[(4 * q + 1) * kStride] - Ut, col[(4 * q + 2) * kStride] - Ut, col[(4 * q + 3) * kStride] - Ut);
-                }
-            }
-#pragma unroll
-            for (int t = 0; t < kTrips; t++) {
-                const int j = j0 + t * NR;
-                if (j < HN) {
-                    float acc = 0.f;
-#pragma unroll
-                    for (int q = 0; q < SPG / 4; q++)
-                        acc += v[t][q].x * wq[4 * q] + v[t][q].y * wq[4 * q + 1] + v[t][q].z * wq[4 * q + 2] + v[t][q].w * wq[4 * q + 3];
-                    rec[2 + j] = acc;
-                }
-            }
-        }
-        return;
-    }
-    for (int j = threadIdx.x; j < HN; j += NT) {
-        const int t = j / nu, c = j - t * nu;
-        const float Ut = sc.Urow[t].v[c];
-        const MPPI_LDS_AS float *col = utab + t * kRow + c;
-        float acc = 0.f;
-        for (int q = 0; q < nlive; q++) acc += (col[q * kStride] - Ut) * s_w[q];
-        rec[2 + j] = acc;
-    }
+    record_rows<2 * kWave, 4 * kWave, 2>(PairRows<T>{sc, utab, nu}, s_w, threadIdx.x, HN, K, k0, rec);
 }
-
 #endif
 
 // The contact-free octet rollout with helper wavefronts (mppi_oct_pair.hpp): 256 threads for 16 consecutive samples - wavefronts
@@ -582,43 +569,13 @@ __global__ __launch_bounds__(4 * kWave) void k_rollout_oct_pair(const DevModel *
     // octet kernel has that from its 256 + 1 registers).  Naming a high AGPR as clobbered puts the wavefront's allocation of
     // the unified register file above one half of it; no instruction is issued for it.
     asm volatile("; one wavefront per SIMD" ::: "a31");
-    constexpr int NT = 4 * kWave;
     // staging as in k_rollout_quad: the robot model, the step constants, the linear lanes' copy of the bodies
-    constexpr int kModelBytes = (int)((offsetof(DevModel, fr) + 15) / 16 * 16);
-    __shared__ __attribute__((aligned(64))) uint4 s_model[kModelBytes / 16];
-    constexpr int kModelTrips = (kModelBytes / 16 + NT - 1) / NT;
-    uint4 mv[kModelTrips];
-#pragma unroll
-    for (int it = 0; it < kModelTrips; it++) {
-        const int i = (int)threadIdx.x + it * NT;
-        mv[it] = reinterpret_cast<const uint4 *>(m)[i < kModelBytes / 16 ? i : 0];
-    }
-    __shared__ __attribute__((aligned(64))) float s_step[sizeof(StepConsts) / sizeof(float)];
-    {
-        const int n = step_const_count(*(CCfg *)cfg);
-        for (int j = threadIdx.x; j < n; j += NT) s_step[j] = step_const_entry(*(CCfg *)cfg, *(CCost *)cost, x0_root, U, j);
-    }
-#pragma unroll
-    for (int it = 0; it < kModelTrips; it++) {
-        const int i = (int)threadIdx.x + it * NT;
-        if (i < kModelBytes / 16) s_model[i] = mv[it];
-    }
-    __shared__ __attribute__((aligned(256))) uint4 s_lin_raw[oct_lin_raw_bytes(T::NB) / 16];
-    LModel &lm = *(LModel *)s_model;
-    LStep &sc = *(LStep *)s_step;
-    MPPI_LDS_AS DevBody *s_lin = oct_lin_place((MPPI_LDS_AS void *)s_lin_raw, &lm.b[0]);
-    if ((int)threadIdx.x < T::NB) {
-        DevBody b = ((const DevModel *)m)->b[threadIdx.x];
-        b.k1 = oct_lin_view(b.k1);
-        s_lin[threadIdx.x] = b;
-    }
+    const auto [lm, sc, s_lin] = rollout_prologue<T, 4 * kWave, true>(m, cfg, cost, x0_root, U);
     static_assert(kPairTableH == kPairMaxH, "the host selects by the table the kernel allocates");
     // the control table and the hand-over ring (mppi_oct_pair.hpp)
     __shared__ __attribute__((aligned(16))) float s_utab[PairLayout<T>::kTable];
     __shared__ f32x4 s_xa[2 * 2 * kWave], s_xb[2 * 2 * kWave];
-    __syncthreads();
-    const int nb = gridDim.x;   // XCD-aware chunk mapping as in k_rollout_quad
-    const int chunk = (nb % 16 == 0) ? (int)(blockIdx.x % 8) * (nb / 8) + (int)(blockIdx.x / 8) : (int)blockIdx.x;
+    const int chunk = xcd_chunk();
     const int wave = (int)(threadIdx.x >> 6), own = wave & 1;   // helper wavefront 2 + w serves owner w
     const bool helper = wave >= 2;
     const int lane = threadIdx.x & (kWave - 1);
@@ -1092,10 +1049,12 @@ __global__ __launch_bounds__(kWave * NW) __attribute__((amdgpu_waves_per_eu(NW))
     // measured slower: the contact loop's constants then occupy VGPRs of code that already spills)
     constexpr int kModelBytes = (int)((offsetof(DevModel, sh) + 15) / 16 * 16);  // header, bodies, links, free bodies
     __shared__ __attribute__((aligned(64))) uint4 s_model[kModelBytes / 16];
+    // (stage_model and xcd_chunk(), written out: with either call the trajectory variant of this kernel with the helper wavefront
+    // - NW = 2, DUMP - came out of the compiler with another register allocation, 18 more SGPR reloads)
     for (int i = threadIdx.x; i < kModelBytes / 16; i += kWave * NW) s_model[i] = reinterpret_cast<const uint4 *>(m)[i];
     __syncthreads();
     LModel &lm = *(LModel *)s_model;
-    const int nb = gridDim.x;  // XCD-aware chunk mapping as in k_rollout_quad (here 128 / (4 SPW) chunks share a line)
+    const int nb = gridDim.x;
     const int chunk = (nb % 16 == 0) ? (int)(blockIdx.x % 8) * (nb / 8) + (int)(blockIdx.x / 8) : (int)blockIdx.x;
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = threadIdx.x / kWave;
@@ -1291,8 +1250,7 @@ __global__ __launch_bounds__(kWave) void k_sim_step_scene_quad(const DevModel *_
     constexpr int NB = T::NB;
     constexpr int kModelBytes = (int)((offsetof(DevModel, sh) + 15) / 16 * 16);  // header, bodies, links, free bodies
     __shared__ __attribute__((aligned(64))) uint4 s_model[kModelBytes / 16];
-    for (int i = threadIdx.x; i < kModelBytes / 16; i += kWave) s_model[i] = reinterpret_cast<const uint4 *>(m)[i];
-    __syncthreads();
+    stage_model<kModelBytes, kWave>(s_model, m);
     LModel &lm = *(LModel *)s_model;
     const int K = cfg->K, nu = cfg->nu;
     const int k = blockIdx.x * 16 + (threadIdx.x >> 2);
@@ -1616,8 +1574,7 @@ __global__ __launch_bounds__(kWave) void k_sim_step_quad(const DevModel *__restr
     constexpr int NB = T::NB;
     constexpr int kModelBytes = (int)((offsetof(DevModel, sh) + 15) / 16 * 16);  // header, bodies, links, free bodies
     __shared__ __attribute__((aligned(64))) uint4 s_model[kModelBytes / 16];
-    for (int i = threadIdx.x; i < kModelBytes / 16; i += kWave) s_model[i] = reinterpret_cast<const uint4 *>(m)[i];
-    __syncthreads();
+    stage_model<kModelBytes, kWave>(s_model, m);
     LModel &lm = *(LModel *)s_model;
     const int K = cfg->K, nu = cfg->nu;
     const int k = blockIdx.x * 16 + (threadIdx.x >> 2);
@@ -1792,6 +1749,24 @@ static_assert(kIoDofFloats == kIoMirrorRoot, "mirror layout");
 constexpr int kIoFloats = kIoDof + kIoDofFloats + 13 * MPPI_MAX_ACTORS + 12;
 
 // ------------------------------------------------------------------------------ context
+// The rollout kernels a context can select, one row each: the name mppi_kernel_info reports, lanes per sample, samples per
+// workgroup (= per record) and wavefronts per workgroup as mppi_kernel_info counts them.
+struct RolloutKind {
+    const char *name;
+    int lanes_per_sample, samples_per_group, waves_per_group;
+};
+enum RolloutKindId { kLane, kQuad, kOct, kOctPair, kScene, kSceneQuad, kSceneOct, kSceneOctPair };
+constexpr RolloutKind kRolloutKinds[] = {
+    {"lane", 1, 64, 1},            // k_rollout
+    {"quad", 4, 16, 1},            // k_rollout_quad
+    {"oct", 8, 16, 2},             // k_rollout_quad<.., 8>: two wavefronts of eight samples
+    {"oct-pair", 8, 16, 4},        // k_rollout_oct_pair: ... and their two helpers
+    {"scene", 1, 64, 1},           // k_rollout_scene
+    {"scene-quad", 4, 16, 1},      // k_rollout_scene_quad<T, 4>
+    {"scene-oct", 8, 8, 1},        // k_rollout_scene_quad<T, 8>
+    {"scene-oct-pair", 8, 8, 1},   // k_rollout_scene_quad<T, 8, 2> (its helper wavefront owns no samples and is not counted)
+};
+
 struct mppi_ctx {
     int device = 0;
     float *h_io = nullptr, *d_io = nullptr;  // the hand-over block and its device address
@@ -1805,17 +1780,16 @@ struct mppi_ctx {
     DevCfg hc;
     DevCost hk;
     int n = 0, A = 0, B = 0, K = 0, H = 0, nu = 0, HN = 0, RF = 0, n_waves = 0;
-    int n_quads = 0;      // wavefronts of the quad- / octet-parallel rollout (16 / 8 samples each)
-    int lanes_per_sample = 1;  // 1 (lane kernels), 4 (quad kernels), 8 (contact scenes: octets)
+    int n_quads = 0;      // records (= workgroups) of the shared-lane rollout kernels (16 / 8 samples each)
+    RolloutKindId rollout = kLane;  // the rollout kernel mppi_create selected
+    const RolloutKind &kind() const { return kRolloutKinds[rollout]; }
+    bool shared_lanes() const { return kind().lanes_per_sample > 1; }  // a sample is spread over a quad or an octet
     float *d_traj = nullptr;          // per-step env states of one rollout set (mppi_rollout_trajectory), allocated on first use
     DevCost *d_cost_none = nullptr;    // a zero cost for those rollouts
     void (*launch_rollout_traj)(mppi_ctx *) = nullptr;
     void (*launch_materialise_traj)(mppi_ctx *, float *, float *, float *, float *) = nullptr;
     void (*launch_materialise_traj_link)(mppi_ctx *, int, float *) = nullptr;  // one robot link of all H*K env-steps (contact-free scenes)
-    bool pair_free = false;    // contact-free octet rollout with helper wavefronts (k_rollout_oct_pair)
-    bool helper_wave = false;  // octet rollout kernel with a second wavefront per sample group for half of the contact pairs
     int n_partials = 0;   // records currently held by d_partials
-    bool quad = false;
     DevModel *d_model = nullptr;
     DevCfg *d_cfg = nullptr;
     DevCost *d_cost = nullptr;
@@ -1906,12 +1880,32 @@ struct TopoEntry {
 
 namespace {
 
-template <class T>
-void launch_rollout_scene_t(mppi_ctx *c) {
-    hipLaunchKernelGGL(k_rollout_scene<T>, dim3(c->n_waves), dim3(kWave), c->lds_bytes, c->stream, c->d_model, c->d_cfg, c->d_cost, c->d_x0_dof,
-                       c->d_x0_root, c->d_U, c->eps_in, c->has_prior ? c->d_prior : nullptr, c->d_du, c->d_S, c->cfg.want_rollouts ? c->d_viz : nullptr,
-                       c->d_partials);
+// Every rollout kernel takes the same first twelve arguments; the shared-lane kernels add the fold counters, the folded records
+// and the wave clock, and - but for k_rollout_oct_pair - the trajectory buffer.  `dump`: the trajectory rollout of the generic
+// Objective mode (the per-step states go to d_traj: zero cost, no visualisation, no fold, no wave clock).
+template <class... P>
+void launch_rollout_kernel(void (*kernel)(P...), int grid, int block, size_t lds, mppi_ctx *c, bool dump = false) {
+    auto go = [&](auto... tail) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, c->stream, c->d_model, c->d_cfg, dump ? c->d_cost_none : c->d_cost, c->d_x0_dof, c->d_x0_root,
+                           c->d_U, c->eps_in, c->has_prior ? c->d_prior : nullptr, c->d_du, c->d_S, !dump && c->cfg.want_rollouts ? c->d_viz : nullptr, c->d_partials, tail...);
+    };
+    unsigned *fold_ctr = !dump && c->fold ? c->d_fold_ctr : nullptr;
+    unsigned long long *wave_clk = !dump && c->wave_clk_on ? c->d_wave_clk : nullptr;
+    if constexpr (sizeof...(P) == 12) go();   // one lane per sample
+    else if constexpr (sizeof...(P) == 15) go(fold_ctr, c->fold_out, wave_clk);
+    else go(fold_ctr, c->fold_out, wave_clk, dump ? c->d_traj : nullptr);
 }
+template <class T>
+void launch_rollout_scene_t(mppi_ctx *c) { launch_rollout_kernel(k_rollout_scene<T>, c->n_waves, kWave, c->lds_bytes, c); }
+
+// The instantiations of k_rollout_scene_quad a tree has: f(SceneRollout<..>{}) for each - what is launched, what has its LDS limit
+// raised and what counts for the static LDS figure come from this one list.
+template <class T, int LPS_, int NW_ = 1, bool DUMP_ = false, bool OSOLVE_ = false>
+struct SceneRollout {
+    static constexpr int LPS = LPS_, NW = NW_;
+    static constexpr bool DUMP = DUMP_, OSOLVE = OSOLVE_;
+    static auto kernel() { return &k_rollout_scene_quad<T, LPS_, NW_, DUMP_, OSOLVE_>; }
+};
 // the octet kernel of a fixed-base tree of more than four bodies runs the solve in the octet layout as well (MPPI_SCENE_SOLVE=quad:
 // the quad-layout solve in both quads, for A/B measurements)
 template <class T>
@@ -1920,59 +1914,46 @@ inline bool scene_oct_solve(const mppi_ctx *c) {
     const char *e = std::getenv("MPPI_SCENE_SOLVE");
     return c->hm.floating == 0 && !(e && std::string(e) == "quad");
 }
-template <class T, int LPS>
-void launch_rollout_scene_quad_t(mppi_ctx *c) {
-    if constexpr (LPS == 8 && kHasOctSolve<T>) {
-        if (scene_oct_solve(c)) {
-            hipLaunchKernelGGL((k_rollout_scene_quad<T, 8, 1, false, true>), dim3(c->n_quads), dim3(kWave), c->lds_bytes_quad * (kWave / LPS) / 16 + c->lds_bytes_table, c->stream, c->d_model, c->d_cfg, c->d_cost, c->d_x0_dof,
-                               c->d_x0_root, c->d_U, c->eps_in, c->has_prior ? c->d_prior : nullptr, c->d_du, c->d_S, c->cfg.want_rollouts ? c->d_viz : nullptr,
-                               c->d_partials, c->fold ? c->d_fold_ctr : nullptr, c->fold_out, c->wave_clk_on ? c->d_wave_clk : nullptr);
-            return;
-        }
+template <class T, class F>
+void for_each_scene_rollout_kernel(F f) {
+    f(SceneRollout<T, 4>{});
+    f(SceneRollout<T, 8>{});
+    f(SceneRollout<T, 8, 1, true>{});
+    if constexpr (kHasOctSolve<T>) {
+        f(SceneRollout<T, 8, 1, false, true>{});
+        f(SceneRollout<T, 8, 1, true, true>{});
     }
-    hipLaunchKernelGGL((k_rollout_scene_quad<T, LPS>), dim3(c->n_quads), dim3(kWave), c->lds_bytes_quad * (kWave / LPS) / 16 + c->lds_bytes_table, c->stream, c->d_model, c->d_cfg, c->d_cost, c->d_x0_dof,
-                       c->d_x0_root, c->d_U, c->eps_in, c->has_prior ? c->d_prior : nullptr, c->d_du, c->d_S, c->cfg.want_rollouts ? c->d_viz : nullptr,
-                       c->d_partials, c->fold ? c->d_fold_ctr : nullptr, c->fold_out, c->wave_clk_on ? c->d_wave_clk : nullptr);
+    if constexpr (T::NB <= 4) {  // short trees: a helper wavefront per sample group (kSplitOctPair)
+        f(SceneRollout<T, 8, 2>{});
+        f(SceneRollout<T, 8, 2, true>{});
+    }
 }
-// octet layout with a helper wavefront per sample group (short trees: kSplitOctPair)
+// dynamic LDS of the kernel with the helper wavefront (+ the helper's accumulator set: bounded by the quad kernel's 16-sample figure)
 template <class T>
 size_t pair_lds_bytes(const mppi_ctx *c) {
     const size_t row = c->lds_bytes_quad / 16 + sizeof(float) * ((size_t)SceneLayout<T>::NF * 27 + 3 * (size_t)c->hm.n_rb + 2 + 6 * kFreeSlots + scene_park_floats<T>());
     return row * (kWave / 8) + c->lds_bytes_table;
 }
+// launches the listed instantiation with `lps` lanes per sample, with or without the helper wavefront (`pair`) and the trajectory dump
 template <class T>
-void launch_rollout_scene_pair_t(mppi_ctx *c) {
-    if constexpr (T::NB <= 4) {
-        hipLaunchKernelGGL((k_rollout_scene_quad<T, 8, 2>), dim3(c->n_quads), dim3(2 * kWave), pair_lds_bytes<T>(c), c->stream, c->d_model, c->d_cfg, c->d_cost, c->d_x0_dof,
-                           c->d_x0_root, c->d_U, c->eps_in, c->has_prior ? c->d_prior : nullptr, c->d_du, c->d_S, c->cfg.want_rollouts ? c->d_viz : nullptr,
-                           c->d_partials, c->fold ? c->d_fold_ctr : nullptr, c->fold_out, c->wave_clk_on ? c->d_wave_clk : nullptr);
-    }
+void launch_rollout_scene_shared(mppi_ctx *c, int lps, bool pair, bool dump) {
+    const bool osolve = kHasOctSolve<T> && lps == 8 && !pair && scene_oct_solve(c);
+    for_each_scene_rollout_kernel<T>([&](auto v) {
+        using V = decltype(v);
+        if (V::LPS != lps || (V::NW == 2) != pair || V::DUMP != dump || V::OSOLVE != osolve) return;
+        size_t lds = c->lds_bytes_quad * (kWave / V::LPS) / 16 + c->lds_bytes_table;
+        if constexpr (V::NW == 2) lds = pair_lds_bytes<T>(c);
+        launch_rollout_kernel(V::kernel(), c->n_quads, kWave * V::NW, lds, c, dump);
+    });
 }
+template <class T, int LPS>
+void launch_rollout_scene_quad_t(mppi_ctx *c) { launch_rollout_scene_shared<T>(c, LPS, false, false); }
+template <class T>
+void launch_rollout_scene_pair_t(mppi_ctx *c) { launch_rollout_scene_shared<T>(c, 8, true, false); }
 // generic Objective mode, whole horizon at once: the fused rollout with the per-step states dumped (cost NONE), then the
 // reference-layout tensors of all H*K env-steps from ONE materialise launch
 template <class T>
-void launch_rollout_scene_traj_t(mppi_ctx *c) {
-    if constexpr (T::NB <= 4) {  // short trees: the kernel with the helper wavefront (pair_lds_bytes is defined below)
-        if (c->helper_wave) {
-            const size_t row = c->lds_bytes_quad / 16 + sizeof(float) * ((size_t)SceneLayout<T>::NF * 27 + 3 * (size_t)c->hm.n_rb + 2 + 6 * kFreeSlots + scene_park_floats<T>());
-            hipLaunchKernelGGL((k_rollout_scene_quad<T, 8, 2, true>), dim3(c->n_quads), dim3(2 * kWave), row * (kWave / 8) + c->lds_bytes_table, c->stream, c->d_model, c->d_cfg, c->d_cost_none,
-                               c->d_x0_dof, c->d_x0_root, c->d_U, c->eps_in, c->has_prior ? c->d_prior : nullptr, c->d_du, c->d_S, (float *)nullptr,
-                               c->d_partials, (unsigned *)nullptr, c->fold_out, (unsigned long long *)nullptr, c->d_traj);
-            return;
-        }
-    }
-    if constexpr (kHasOctSolve<T>) {
-        if (scene_oct_solve(c)) {
-            hipLaunchKernelGGL((k_rollout_scene_quad<T, 8, 1, true, true>), dim3(c->n_quads), dim3(kWave), c->lds_bytes_quad * (kWave / 8) / 16 + c->lds_bytes_table, c->stream, c->d_model, c->d_cfg, c->d_cost_none, c->d_x0_dof,
-                               c->d_x0_root, c->d_U, c->eps_in, c->has_prior ? c->d_prior : nullptr, c->d_du, c->d_S, (float *)nullptr,
-                               c->d_partials, (unsigned *)nullptr, c->fold_out, (unsigned long long *)nullptr, c->d_traj);
-            return;
-        }
-    }
-    hipLaunchKernelGGL((k_rollout_scene_quad<T, 8, 1, true>), dim3(c->n_quads), dim3(kWave), c->lds_bytes_quad * (kWave / 8) / 16 + c->lds_bytes_table, c->stream, c->d_model, c->d_cfg, c->d_cost_none, c->d_x0_dof,
-                       c->d_x0_root, c->d_U, c->eps_in, c->has_prior ? c->d_prior : nullptr, c->d_du, c->d_S, (float *)nullptr,
-                       c->d_partials, (unsigned *)nullptr, c->fold_out, (unsigned long long *)nullptr, c->d_traj);
-}
+void launch_rollout_scene_traj_t(mppi_ctx *c) { launch_rollout_scene_shared<T>(c, 8, T::NB <= 4 && c->rollout == kSceneOctPair, true); }
 template <class T>
 void launch_materialise_scene_traj_t(mppi_ctx *c, float *dof, float *root, float *rb, float *cf) {
     const size_t HK = (size_t)c->H * c->K;
@@ -1998,29 +1979,15 @@ void launch_materialise_scene_t(mppi_ctx *c, float *dof, float *root, float *rb,
 }
 template <class T>
 hipError_t raise_lds_limit(size_t lane_bytes, size_t quad_bytes) {  // lane_bytes == 0: the one-lane kernels are not used
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rollout_scene_quad<T, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)quad_bytes);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rollout_scene_quad<T, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)quad_bytes);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rollout_scene_quad<T, 8, 1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)quad_bytes);
-    if (e != hipSuccess) return e;
-    if constexpr (kHasOctSolve<T>) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rollout_scene_quad<T, 8, 1, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)quad_bytes);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rollout_scene_quad<T, 8, 1, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)quad_bytes);
-        if (e != hipSuccess) return e;
-    }
-    if constexpr (T::NB <= 4) {  // (+ the helper's accumulator set: bounded by the quad kernel's 16-sample figure)
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rollout_scene_quad<T, 8, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)quad_bytes);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rollout_scene_quad<T, 8, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)quad_bytes);
-        if (e != hipSuccess) return e;
-    }
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sim_step_scene_quad<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)quad_bytes);
+    auto raise = [](auto kernel, size_t bytes) { return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); };
+    hipError_t e = hipSuccess;
+    for_each_scene_rollout_kernel<T>([&](auto v) {
+        if (e == hipSuccess) e = raise(decltype(v)::kernel(), quad_bytes);
+    });
+    if (e == hipSuccess) e = raise(&k_sim_step_scene_quad<T>, quad_bytes);
     if (e != hipSuccess || lane_bytes == 0) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rollout_scene<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lane_bytes);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(&k_sim_step_scene<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lane_bytes);
+    e = raise(&k_rollout_scene<T>, lane_bytes);
+    return e != hipSuccess ? e : raise(&k_sim_step_scene<T>, lane_bytes);
 }
 
 // static __shared__ of the scene kernels (staged start state, fold tickets, step constants, the wave-shared model copy): it
@@ -2028,58 +1995,28 @@ hipError_t raise_lds_limit(size_t lane_bytes, size_t quad_bytes) {  // lane_byte
 template <class T>
 size_t static_lds_bytes_scene() {
     size_t mx = 0;
-    auto ask = [&](const void *f) {
+    auto ask = [&](auto kernel) {
         hipFuncAttributes a;
-        if (hipFuncGetAttributes(&a, f) == hipSuccess && a.sharedSizeBytes > mx) mx = a.sharedSizeBytes;
+        if (hipFuncGetAttributes(&a, reinterpret_cast<const void *>(kernel)) == hipSuccess && a.sharedSizeBytes > mx) mx = a.sharedSizeBytes;
         else (void)hipGetLastError();
     };
-    ask(reinterpret_cast<const void *>(&k_rollout_scene_quad<T, 4>));
-    ask(reinterpret_cast<const void *>(&k_rollout_scene_quad<T, 8>));
-    ask(reinterpret_cast<const void *>(&k_rollout_scene_quad<T, 8, 1, true>));
-    if constexpr (kHasOctSolve<T>) {
-        ask(reinterpret_cast<const void *>(&k_rollout_scene_quad<T, 8, 1, false, true>));
-        ask(reinterpret_cast<const void *>(&k_rollout_scene_quad<T, 8, 1, true, true>));
-    }
-    if constexpr (T::NB <= 4) {
-        ask(reinterpret_cast<const void *>(&k_rollout_scene_quad<T, 8, 2>));
-        ask(reinterpret_cast<const void *>(&k_rollout_scene_quad<T, 8, 2, true>));
-    }
-    ask(reinterpret_cast<const void *>(&k_sim_step_scene_quad<T>));
+    for_each_scene_rollout_kernel<T>([&](auto v) { ask(decltype(v)::kernel()); });
+    ask(&k_sim_step_scene_quad<T>);
     return mx;
 }
 
 template <class T>
-void launch_rollout_quad_t(mppi_ctx *c) {
-    hipLaunchKernelGGL(k_rollout_quad<T>, dim3(c->n_quads), dim3(kWave), 0, c->stream, c->d_model, c->d_cfg, c->d_cost, c->d_x0_dof, c->d_x0_root,
-                       c->d_U, c->eps_in, c->has_prior ? c->d_prior : nullptr, c->d_du, c->d_S, c->cfg.want_rollouts ? c->d_viz : nullptr, c->d_partials,
-                       c->fold ? c->d_fold_ctr : nullptr, c->fold_out, c->wave_clk_on ? c->d_wave_clk : nullptr);
-}
+void launch_rollout_quad_t(mppi_ctx *c) { launch_rollout_kernel(k_rollout_quad<T>, c->n_quads, kWave, 0, c); }
 // the same rollout with the articulated-body solve in the octet layout (8 lanes per sample, K/8 wavefronts; mppi_oct.hpp)
 template <class T>
-void launch_rollout_oct_t(mppi_ctx *c) {
-    hipLaunchKernelGGL((k_rollout_quad<T, false, 8>), dim3(c->n_quads), dim3(2 * kWave), 0, c->stream, c->d_model, c->d_cfg, c->d_cost, c->d_x0_dof, c->d_x0_root,
-                       c->d_U, c->eps_in, c->has_prior ? c->d_prior : nullptr, c->d_du, c->d_S, c->cfg.want_rollouts ? c->d_viz : nullptr, c->d_partials,
-                       c->fold ? c->d_fold_ctr : nullptr, c->fold_out, c->wave_clk_on ? c->d_wave_clk : nullptr);
-}
+void launch_rollout_oct_t(mppi_ctx *c) { launch_rollout_kernel(k_rollout_quad<T, false, 8>, c->n_quads, 2 * kWave, 0, c); }
 // ... and with two helper wavefronts per workgroup (controls, cost and output off the owners' instruction stream)
 template <class T>
-void launch_rollout_oct_pair_t(mppi_ctx *c) {
-    hipLaunchKernelGGL(k_rollout_oct_pair<T>, dim3(c->n_quads), dim3(4 * kWave), 0, c->stream, c->d_model, c->d_cfg, c->d_cost, c->d_x0_dof, c->d_x0_root,
-                       c->d_U, c->eps_in, c->has_prior ? c->d_prior : nullptr, c->d_du, c->d_S, c->cfg.want_rollouts ? c->d_viz : nullptr, c->d_partials,
-                       c->fold ? c->d_fold_ctr : nullptr, c->fold_out, c->wave_clk_on ? c->d_wave_clk : nullptr);
-}
+void launch_rollout_oct_pair_t(mppi_ctx *c) { launch_rollout_kernel(k_rollout_oct_pair<T>, c->n_quads, 4 * kWave, 0, c); }
 template <class T>
-void launch_rollout_oct_traj_t(mppi_ctx *c) {
-    hipLaunchKernelGGL((k_rollout_quad<T, true, 8>), dim3(c->n_quads), dim3(2 * kWave), 0, c->stream, c->d_model, c->d_cfg, c->d_cost_none, c->d_x0_dof, c->d_x0_root,
-                       c->d_U, c->eps_in, c->has_prior ? c->d_prior : nullptr, c->d_du, c->d_S, (float *)nullptr, c->d_partials,
-                       (unsigned *)nullptr, c->fold_out, (unsigned long long *)nullptr, c->d_traj);
-}
+void launch_rollout_oct_traj_t(mppi_ctx *c) { launch_rollout_kernel(k_rollout_quad<T, true, 8>, c->n_quads, 2 * kWave, 0, c, true); }
 template <class T>
-void launch_rollout_traj_t(mppi_ctx *c) {
-    hipLaunchKernelGGL((k_rollout_quad<T, true>), dim3(c->n_quads), dim3(kWave), 0, c->stream, c->d_model, c->d_cfg, c->d_cost_none, c->d_x0_dof, c->d_x0_root,
-                       c->d_U, c->eps_in, c->has_prior ? c->d_prior : nullptr, c->d_du, c->d_S, (float *)nullptr, c->d_partials,
-                       (unsigned *)nullptr, c->fold_out, (unsigned long long *)nullptr, c->d_traj);
-}
+void launch_rollout_traj_t(mppi_ctx *c) { launch_rollout_kernel(k_rollout_quad<T, true>, c->n_quads, kWave, 0, c, true); }
 template <class T>
 void launch_materialise_traj_t(mppi_ctx *c, float *dof, float *root, float *rb, float *cf) {
     const size_t HK = (size_t)c->H * c->K;
@@ -2108,10 +2045,7 @@ void launch_eval_cost_t(mppi_ctx *c, int n, const float *dof, const float *root,
     hipLaunchKernelGGL(k_eval_cost<T>, dim3((n + kWave - 1) / kWave), dim3(kWave), 0, c->stream, c->d_model, c->d_cost, n, dof, root, rb, cf, out);
 }
 template <class T>
-void launch_rollout_t(mppi_ctx *c) {
-    hipLaunchKernelGGL(k_rollout<T>, dim3(c->n_waves), dim3(kWave), 0, c->stream, c->d_model, c->d_cfg, c->d_cost, c->d_x0_dof, c->d_x0_root,
-                       c->d_U, c->eps_in, c->has_prior ? c->d_prior : nullptr, c->d_du, c->d_S, c->cfg.want_rollouts ? c->d_viz : nullptr, c->d_partials);
-}
+void launch_rollout_t(mppi_ctx *c) { launch_rollout_kernel(k_rollout<T>, c->n_waves, kWave, 0, c); }
 template <class T>
 void launch_sim_step_t(mppi_ctx *c, int mode, int t, const float *u_ext) {
     hipLaunchKernelGGL(k_sim_step<T>, dim3(c->n_waves), dim3(kWave), 0, c->stream, c->d_model, c->d_cfg, mode, t, u_ext, c->d_x0_root, c->d_U,
