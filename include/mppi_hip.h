@@ -463,6 +463,8 @@ int mppi_update_step_world(mppi_ctx_t *planner, const float *records_dev, int n_
 /* ---- instrumentation (reference has only print(FPS), examples/panda/world.py:53-59) */
 int mppi_set_profiling(mppi_ctx_t *ctx, int on);            /* hipEvent brackets on the context's stream: 0 off, n >= 1 every n-th launch */
 int mppi_kernel_ms(mppi_ctx_t *ctx, int which, float *ms); /* mean launch duration since profiling was enabled: 0 rollout 1 reduce 2 update */
+/* "topology=<tree> rollout=<kernel> K=.. H=.. nu=.. waves=.. block=.. bytes_alg=.. step=<lane|quad|scene|scene-quad>": the rollout
+ * kernel of mppi_rollout / mppi_command and, last, the env-step kernel of mppi_sim_step* (both selected by mppi_create) */
 int mppi_kernel_info(mppi_ctx_t *ctx, char *buf, int buflen);
 /* per-wavefront residency of the quad rollout kernels: start / end of every wavefront of the LAST rollout in ticks of the
  * 100 MHz constant clock (s_memrealtime), [n_wavefronts][2] - load-balance evidence (tools/exp/wave_balance.py) */

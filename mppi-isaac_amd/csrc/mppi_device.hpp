@@ -823,7 +823,15 @@ MPPI_HD void step(CModel &m0, const float *root, float *q, float *qd, const floa
                 kdh[i] = 0.f;
             }
         });
-        if (any) aba_world<T>(*launder(mp), P, qd, tau, kdh, qdd);
+        if (any) {
+            // (drives held at their limit are solved without the implicit damping that hides the cancellation in S^T I^A S about
+            // the world origin: this solve is taken about the last body's origin - mppi_quad.hpp quad_step)
+            if constexpr (NB > 0) {
+                const V3 org = P.p[NB - 1];
+                static_for<0, NB>([&](auto ic) MPPI_LAMBDA { P.p[ic] = P.p[ic] - org; });
+            }
+            aba_world<T>(*launder(mp), P, qd, tau, kdh, qdd);
+        }
         static_for<0, NB>([&](auto ic) MPPI_LAMBDA {
             constexpr int i = ic;
             const BodyK1 b = load_block<BodyK1>(m.b[i].k1);

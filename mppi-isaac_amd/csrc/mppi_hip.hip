@@ -536,6 +536,7 @@ int mppi_create(const mppi_model_t *model, const mppi_config_t *cfg, int device,
                 c->launch_materialise_traj = e->materialise_scene_traj;
             }
             c->launch_sim_step = quad ? e->sim_step_scene_quad : e->sim_step_scene;  // (the K = 1 world included: one quad)
+            c->step_name = quad ? "scene-quad" : "scene";
             c->step_feeds_back = quad;
             c->launch_materialise = e->materialise_scene;
             // (large scenes - e.g. the 12-DoF mobile manipulator with table and block - do not fit the one-lane kernels' 64 rows
@@ -583,7 +584,9 @@ int mppi_create(const mppi_model_t *model, const mppi_config_t *cfg, int device,
             // the reference's examples waits for this kernel every control iteration); MPPI_WORLD_STEP=lane keeps the one-lane kernel
             const char *ws = std::getenv("MPPI_WORLD_STEP");
             const bool world_quad = cfg->num_samples == 1 && !(ws && std::string(ws) == "lane");
-            c->launch_sim_step = (quad && (cfg->num_samples >= 64 || world_quad)) ? e->sim_step_quad : e->sim_step;
+            const bool step_quad = quad && (cfg->num_samples >= 64 || world_quad);
+            c->launch_sim_step = step_quad ? e->sim_step_quad : e->sim_step;
+            c->step_name = step_quad ? "quad" : "lane";
             c->launch_materialise = e->materialise;
         }
         break;
@@ -1395,9 +1398,9 @@ int mppi_kernel_info(mppi_ctx_t *c, char *buf, int buflen) {
     CTX_TRY(c);
     // (a cost program on a contact-free scene runs on the one-lane kernel whatever was selected at mppi_create: mppi_set_cost)
     const RolloutKind &k = c->prog_lane ? kRolloutKinds[kLane] : c->kind();
-    std::snprintf(buf, buflen, "topology=%s rollout=%s K=%d H=%d nu=%d waves=%d block=%d bytes_alg=%zu", c->topo.c_str(), k.name, c->K, c->H, c->nu,
+    std::snprintf(buf, buflen, "topology=%s rollout=%s K=%d H=%d nu=%d waves=%d block=%d bytes_alg=%zu step=%s", c->topo.c_str(), k.name, c->K, c->H, c->nu,
                   (c->K + k.samples_per_group - 1) / k.samples_per_group * k.waves_per_group, kWave,
-                  (size_t)4 * (3 * (size_t)c->K * c->HN + 2 * (size_t)c->K + c->HN));
+                  (size_t)4 * (3 * (size_t)c->K * c->HN + 2 * (size_t)c->K + c->HN), c->step_name);
     return MPPI_OK;
 }
 

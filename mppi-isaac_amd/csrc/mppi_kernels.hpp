@@ -1825,6 +1825,7 @@ struct mppi_ctx {
     void (*launch_rollout_lane)(mppi_ctx *) = nullptr;  // one-lane kernel of a contact-free scene (cost programs)
     bool prog_lane = false;
     void (*launch_sim_step)(mppi_ctx *, int, int, const float *) = nullptr;
+    const char *step_name = "";  // the kernel launch_sim_step points to, as mppi_kernel_info reports it: lane | quad | scene | scene-quad
     void (*launch_materialise)(mppi_ctx *, float *, float *, float *, float *) = nullptr;
     void (*launch_combine_world)(mppi_ctx *, const float *, int, mppi_ctx *) = nullptr;  // fused closed-loop tail (quad scenes)
     void (*launch_eval_cost)(mppi_ctx *, int, const float *, const float *, const float *, const float *, float *) = nullptr;

@@ -752,6 +752,16 @@ MPPI_HD void quad_step(M &m0, QPose<T, JT> &P, QF *q, QF *qd, const QF *target, 
                 tau[i] = sat ? qwhere_gt(tt[i], qrep(0.f), eff, -eff) : tau[i];
                 kdh[i] = sat ? qrep(0.f) : kdh[i];
             });
+            // The solve takes its spatial quantities about the origin of P's positions.  About the WORLD origin the joint-space
+            // inertia S^T I^A S of a wrist joint (1e-3 kg m^2) is what is left of terms of m |c|^2 (kg m^2); the implicit drive
+            // adds kd h = 15 to it, a drive held at its limit does not - its acceleration carried that cancellation (qd 5e-5 off
+            // after a step with the arm at the world origin, 6e-3 with its base 8 m away).  This solve is therefore taken about
+            // the LAST body's origin (the light joints are the distal ones); the solve is invariant under the shift, and P is
+            // rebuilt from the base pose below.  (Quad layout; the octet layout's pose rows are not the quad's.)
+            if constexpr (!AB::kFusedLimitCheck && NB > 0) {
+                const QF org = P.pos(NB - 1);
+                static_for<0, NB>([&](auto ic) MPPI_LAMBDA { P.R2p[ic].y = P.R2p[ic].y - org; });
+            }
             ab.template aba<T>(*launder(mp), P, qd, tau, kdh, qdd, lim);
         }
         // the kinematic blocks of the NEXT pose are requested here: they carry the joint ranges the integration needs, and
