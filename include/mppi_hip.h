@@ -421,6 +421,27 @@ int mppi_eval_cost(mppi_ctx_t *ctx, int n, const float *dof_host, const float *r
  *      replaces IsaacGymWrapper.apply_robot_cmd + step (isaacgym_wrapper.py:524-572,639-655)
  *      and the four gym state tensors (:186-199). */
 int mppi_sim_reset(mppi_ctx_t *ctx);                       /* all K envs <- current x0              */
+/* Per-env states in: replaces gym's set_dof_state_tensor / set_actor_root_state_tensor(_indexed) behind the reference's
+ * set_actor_dof_state and its pushes of `_root_state` (isaacgym_wrapper.py:399-400, :744-746), where `_dof_state [K][2n]` and
+ * `_root_state [K][A][13]` are writable tensors of all envs.  Device tensors in the reference layouts; NULL = leave that part of
+ * the envs as it is (both NULL: MPPI_EINVAL).
+ *   mppi_sim_set_states          env j <- row j, all K envs
+ *   mppi_sim_set_states_indexed  env env_ids[j] <- row j for j < n_ids (env_ids: device int32).  An id outside [0, K) is skipped
+ *                                without touching memory; an id listed twice gets ONE of its rows, which one is unspecified
+ *   mppi_sim_reset_indexed       the listed envs <- current x0, their cost and control-cost accumulators zeroed: mppi_sim_reset
+ *                                for those envs alone
+ * PER ENV are the DOF state, the root rows of MOVING robot bases and the root rows of free (non-fixed box / sphere) actors.  The
+ * rows of fixed actors and of a fixed-base robot are SHARED by all envs: they stay what mppi_set_state made them, and those rows
+ * of root_dev are not read.  On a contact-free context (fixed-base robot, no free actor, no contact pair) nothing of the root is
+ * per env: root_dev is accepted and ignored.  The contact forces of every addressed env are zeroed (a state that has not been
+ * stepped reports none, as after mppi_sim_reset); the set_states calls leave the cost accumulators alone.
+ * Stream-ordered on the context's stream, kernel launches only - no synchronise, no copy operation: they can sit in a captured
+ * graph, and the input tensors must stay valid until the stream has passed them.  x0 is untouched: a later mppi_sim_reset, or a
+ * planner's command, returns every env to it. */
+int mppi_sim_set_states(mppi_ctx_t *ctx, const float *dof_dev /* [K][2n] or NULL */, const float *root_dev /* [K][A][13] or NULL */);
+int mppi_sim_set_states_indexed(mppi_ctx_t *ctx, const int32_t *env_ids_dev, int n_ids,
+                                const float *dof_dev /* [n_ids][2n] or NULL */, const float *root_dev /* [n_ids][A][13] or NULL */);
+int mppi_sim_reset_indexed(mppi_ctx_t *ctx, const int32_t *env_ids_dev, int n_ids);   /* those envs <- x0 */
 int mppi_sim_step(mppi_ctx_t *ctx, const float *u_dev, int u_is_shared); /* u [K][nu] (AoS) or [nu] */
 int mppi_sim_step_horizon(mppi_ctx_t *ctx, int t);         /* u = clamp(U[t]+eps[t]) per sample     */
 /* (ABI 8) the host side of the reference's world loop (examples/<x>/world.py:35-44: torch_to_bytes(sim._dof_state),

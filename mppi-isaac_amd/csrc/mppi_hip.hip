@@ -1237,6 +1237,40 @@ int mppi_sim_reset(mppi_ctx_t *c) {
         hipLaunchKernelGGL(k_sim_reset_scene, dim3((c->K + 255) / 256), dim3(256), 0, c->stream, c->d_model, c->K, c->d_x0_root, c->d_base, c->d_fr, c->d_cf, c->free_slots);
     return launch_check();
 }
+namespace {
+// rows 0 .. n_rows-1 of the per-env inputs (pitch 0: the shared x0 in every row) -> the envs env_ids names (nullptr: env j <- row j).
+// Launches only: stream-ordered, nothing to wait for.  Contact scenes: the contact forces of the addressed envs are zeroed whichever
+// input is given (root_src == nullptr: their root rows stay)
+int scatter_states(mppi_ctx *c, const int32_t *env_ids, int n_rows, const float *dof_src, size_t dof_pitch, const float *root_src, size_t root_pitch, bool zero_costs) {
+    if (n_rows == 0) return MPPI_OK;
+    const dim3 grid((n_rows + 255) / 256), block(256);
+    if (dof_src)
+        hipLaunchKernelGGL(k_sim_set_states, grid, block, 0, c->stream, c->K, c->n, env_ids, n_rows, dof_src, dof_pitch, c->d_q, c->d_qd, c->d_S, c->d_ctrl, zero_costs ? 1 : 0);
+    if (c->scene)
+        hipLaunchKernelGGL(k_sim_set_states_scene, grid, block, 0, c->stream, c->d_model, c->K, env_ids, n_rows, root_src, root_pitch, c->d_x0_root, c->d_base, c->d_fr, c->d_cf,
+                           c->free_slots);
+    return launch_check();
+}
+}  // namespace
+/* per-env states in: what gym's set_dof_state_tensor / set_actor_root_state_tensor(_indexed) do behind the reference's
+ * set_actor_dof_state and its root-state pushes (isaacgym_wrapper.py:399-400, :744-746) */
+int mppi_sim_set_states(mppi_ctx_t *c, const float *dof_dev, const float *root_dev) {
+    CTX_TRY(c);
+    if (!dof_dev && !root_dev) return fail(MPPI_EINVAL, "mppi_sim_set_states: neither a dof nor a root tensor");
+    return scatter_states(c, nullptr, c->K, dof_dev, 2 * (size_t)c->n, root_dev, 13 * (size_t)c->A, false);
+}
+int mppi_sim_set_states_indexed(mppi_ctx_t *c, const int32_t *env_ids_dev, int n_ids, const float *dof_dev, const float *root_dev) {
+    CTX_TRY(c);
+    if (n_ids < 0 || (n_ids > 0 && !env_ids_dev)) return fail(MPPI_EINVAL, "mppi_sim_set_states_indexed: null env ids or a negative count");
+    if (!dof_dev && !root_dev) return fail(MPPI_EINVAL, "mppi_sim_set_states_indexed: neither a dof nor a root tensor");
+    return scatter_states(c, env_ids_dev, n_ids, dof_dev, 2 * (size_t)c->n, root_dev, 13 * (size_t)c->A, false);
+}
+int mppi_sim_reset_indexed(mppi_ctx_t *c, const int32_t *env_ids_dev, int n_ids) {
+    CTX_TRY(c);
+    if (n_ids < 0 || (n_ids > 0 && !env_ids_dev)) return fail(MPPI_EINVAL, "mppi_sim_reset_indexed: null env ids or a negative count");
+    c->partials_valid = false;
+    return scatter_states(c, env_ids_dev, n_ids, c->d_x0_dof, 0, c->d_x0_root, 0, true);
+}
 int mppi_sim_step(mppi_ctx_t *c, const float *u_dev, int u_is_shared) {
     CTX_TRY(c);
     if (!u_dev) return fail(MPPI_EINVAL, "null command");

@@ -1392,6 +1392,36 @@ __global__ void k_sim_reset_scene(const DevModel *__restrict__ m, int K, const f
         for (int j = 0; j < 13; j++) fr_[(size_t)(f * 13 + j) * K + k] = f < m->n_free ? x0_root[13 * m->fr[f].actor + j] : 0.f;
     for (int j = 0; j < 3 * m->n_rb; j++) cf_[(size_t)j * K + k] = 0.f;
 }
+// env that row j of a per-env input goes to: j itself (env_ids == nullptr), else env_ids[j]; -1: no such row, or an id outside
+// [0, K) - the caller then touches no memory
+__device__ __forceinline__ int addressed_env(const int32_t *__restrict__ env_ids, int n_rows, int K, int j) {
+    if (j >= n_rows) return -1;
+    const int k = env_ids != nullptr ? env_ids[j] : j;
+    return k >= 0 && k < K ? k : -1;
+}
+// the addressed envs <- their own root rows: row j of `src` (pitch `src_pitch` floats: 13 * n_actors for per-env rows
+// [n_rows][A][13], 0 for ONE shared state such as x0_root; src == nullptr: the root rows stay as they are) goes to the env of
+// addressed_env.  Per env are the rows of the MOVING bases and of the free actors only: a fixed-base robot's rows come from
+// x0_root as in k_sim_reset_scene, the rows of fixed actors are never stored per env - neither is read from `src`.  The contact
+// forces of every addressed env are zeroed: a state that has not been stepped reports none.  Two rows for one env: one of them wins.
+__global__ void k_sim_set_states_scene(const DevModel *__restrict__ m, int K, const int32_t *__restrict__ env_ids, int n_rows,
+                                       const float *__restrict__ src, size_t src_pitch, const float *__restrict__ x0_root, float *__restrict__ base_,
+                                       float *__restrict__ fr_, float *__restrict__ cf_, int free_slots) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    const int k = addressed_env(env_ids, n_rows, K, j);
+    if (k < 0) return;
+    if (src != nullptr) {
+        const float *row = src + (size_t)j * src_pitch;
+        const float *bases = m->floating ? row : x0_root;
+        for (int r = 0; r < m->n_bases; r++) {
+            const int actor = r == 0 ? m->robot_actor : m->xbase_actor[r - 1];
+            for (int i = 0; i < 13; i++) base_[(size_t)(13 * r + i) * K + k] = bases[13 * actor + i];
+        }
+        for (int f = 0; f < free_slots; f++)
+            for (int i = 0; i < 13; i++) fr_[(size_t)(f * 13 + i) * K + k] = f < m->n_free ? row[13 * m->fr[f].actor + i] : 0.f;
+    }
+    for (int i = 0; i < 3 * m->n_rb; i++) cf_[(size_t)i * K + k] = 0.f;
+}
 // planner.x0_root rows of the robot base / free actors <- world env 0
 __global__ void k_root_from_world(const DevModel *__restrict__ m, const float *__restrict__ wbase, const float *__restrict__ wfr, float *__restrict__ x0_root) {
     const int j = threadIdx.x;
@@ -1514,6 +1544,24 @@ __global__ void k_sim_reset(int K, int n, const float *__restrict__ x0_dof, floa
     }
     S[k] = 0.f;
     ctrl[k] = 0.f;
+}
+// the addressed envs <- their own DOF state: row j of `src` (interleaved q, qd; pitch 2n for per-env rows [n_rows][2n], 0 for ONE
+// shared state such as x0_dof) goes to the env of addressed_env (above k_sim_set_states_scene).  zero_costs: the cost and
+// control-cost accumulators of those envs are zeroed as k_sim_reset does for all (an indexed reset); otherwise they stay.
+__global__ void k_sim_set_states(int K, int n, const int32_t *__restrict__ env_ids, int n_rows, const float *__restrict__ src, size_t src_pitch,
+                                 float *__restrict__ q, float *__restrict__ qd, float *__restrict__ S, float *__restrict__ ctrl, int zero_costs) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    const int k = addressed_env(env_ids, n_rows, K, j);
+    if (k < 0) return;
+    const float *row = src + (size_t)j * src_pitch;
+    for (int i = 0; i < n; i++) {
+        q[(size_t)i * K + k] = row[2 * i];
+        qd[(size_t)i * K + k] = row[2 * i + 1];
+    }
+    if (zero_costs) {
+        S[k] = 0.f;
+        ctrl[k] = 0.f;
+    }
 }
 
 // mode 0: u_ext is [K][nu] (reference layout), mode 1: u_ext is one shared [nu], mode 2: horizon step t

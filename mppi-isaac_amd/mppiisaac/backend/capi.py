@@ -144,6 +144,9 @@ _SIGNATURES = {
     "mppi_get_perturbations": (C.c_int, [_vp, _fp]),
     "mppi_get_noise": (C.c_int, [_vp, _fp]),
     "mppi_sim_reset": (C.c_int, [_vp]),
+    "mppi_sim_set_states": (C.c_int, [_vp, _vp, _vp]),
+    "mppi_sim_set_states_indexed": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
+    "mppi_sim_reset_indexed": (C.c_int, [_vp, _vp, C.c_int]),
     "mppi_sim_step": (C.c_int, [_vp, _vp, C.c_int]),
     "mppi_sim_step_horizon": (C.c_int, [_vp, C.c_int]),
     "mppi_sim_step_host": (C.c_int, [_vp, _fp]),

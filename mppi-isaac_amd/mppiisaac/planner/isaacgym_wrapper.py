@@ -1067,9 +1067,98 @@ class IsaacGymWrapper:
         self._set_root_columns(idx, 0, 13, state_tensor)
 
     def set_actor_dof_state(self, state) -> None:
-        """`dof_mode: position` path of the reference (:399-400): overwrite the interleaved (q, qd) DOF state"""
+        """`dof_mode: position` path of the reference (:399-400): overwrite the interleaved (q, qd) DOF state
+        (ONE state, the first 2n floats, for every env; a [K, 2n] tensor with a row per env goes through set_dof_state_tensor)"""
         st = torch.as_tensor(state, dtype=torch.float32).reshape(-1)[: 2 * self.scene.n_dof]
         self._push_single_state(st.cpu().numpy(), self._root_state[0].cpu().numpy())
+
+    # ------------------------------------------------------------------ per-env states in (gym's tensor API behind reference :399-400, :744-746)
+    # The reference edits `_dof_state [K, 2n]` / `_root_state [K, A, 13]` in place and hands the tensor of ALL envs to gym.  The
+    # same idiom works here - `sim._dof_state[k] = ...; sim.set_dof_state_tensor()` - with one rule: edit both tensors before the
+    # first set call, since reading a state tensor after a set call refreshes it from the simulator.  Per env are the DOF state
+    # and the root rows of moving robot bases and of free (non-fixed) box / sphere actors; the rows of fixed actors and of a
+    # fixed-base robot are one shared state (set_actor_position_by_name and its kin move them in every env).
+    def _per_env_actors(self):
+        m = self._c_model
+        moving = [m.robot_actor] + [m.extra_base_actor[r] for r in range(m.n_extra_bases)] if not m.actors[m.robot_actor].fixed else []
+        return moving + [a for a in range(m.n_actors) if a != m.robot_actor and not m.actors[a].fixed and m.actors[a].type != capi.ACTOR_ROBOT]
+
+    def _env_ids(self, env_ids):
+        ids = torch.as_tensor(env_ids).reshape(-1).to("cpu", torch.int64)
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= self.num_envs):
+            raise ValueError(f"env ids must lie in [0, {self.num_envs}): got {ids.tolist()}")
+        return ids.to(self.device, torch.int32)
+
+    def _per_env_input(self, key, state, rows):
+        """the tensor a set call pushes: `state` as contiguous float32 on the sim's device, or the wrapper's own tensor"""
+        shape = (rows, 2 * self.scene.n_dof) if key == "dof" else (rows, len(self.env_cfg), 13)
+        if state is None:
+            if rows != self.num_envs:
+                raise ValueError("state=None pushes the wrapper's own tensor of all envs: index it with env_ids for an indexed call")
+            return self._state_t_own[key]    # (as it stands: reading it through the property would refresh it and lose the caller's edits)
+        t = torch.as_tensor(state).to(self.device, torch.float32).contiguous()
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{key} state of shape {tuple(t.shape)}, expected {shape}")
+        return t
+
+    def _check_shared_rows(self, root):
+        """rows of fixed actors / of a fixed-base robot are not per env: an input that changes one is refused (one device-to-host
+        read), it would otherwise be dropped silently"""
+        per_env = self._per_env_actors()
+        shared = [a for a in range(len(self.env_cfg)) if a not in per_env]
+        if not shared:
+            return
+        now = torch.empty((self.num_envs, len(self.env_cfg), 13), dtype=torch.float32, device=self.device)
+        capi.check(self._lib, self._lib.mppi_sim_materialise(self._ctx, None, _dev_ptr(now), None, None))
+        x0 = now[0, shared]              # (the materialise kernel copies the shared rows from x0 into every env)
+        differs = (root[:, shared] != x0[None]).any(dim=2).any(dim=0).cpu()
+        for a, bad in zip(shared, differs.tolist()):
+            if bad:
+                raise ValueError(f"root rows of actor '{self.env_cfg[a].name}' differ from the shared state: a fixed actor (or a fixed-base "
+                                 "robot) has ONE pose for all envs - move it with set_actor_position_by_name / set_root_state_tensor_by_actor_idx")
+
+    def _scatter(self, key, state, env_ids=None):
+        """rows of `state` -> the DOF (key "dof") or root (key "root") state of the envs env_ids names (None: all, row k -> env k)"""
+        if self._state_t is not self._state_t_own:
+            raise RuntimeError("per-env states cannot be set inside a planner's horizon view")
+        ids = None if env_ids is None else self._env_ids(env_ids)
+        rows = self.num_envs if ids is None else int(ids.numel())
+        t = self._per_env_input(key, state, rows)
+        self._reset_envs_if_needed()     # a pending broadcast of x0 comes first: the part that is not given stays at x0
+        if key == "root":
+            self._check_shared_rows(t)
+        dof, root = (_dev_ptr(t), None) if key == "dof" else (None, _dev_ptr(t))
+        if ids is None:
+            capi.check(self._lib, self._lib.mppi_sim_set_states(self._ctx, dof, root))
+        else:
+            capi.check(self._lib, self._lib.mppi_sim_set_states_indexed(self._ctx, _dev_ptr(ids), rows, dof, root))
+        self._stale = True               # (the K = 1 mirror with it: the next read materialises and mirrors again, as after step())
+
+    def set_dof_state_tensor(self, state=None) -> None:
+        """gym.set_dof_state_tensor: row k of `state` [K, 2n] (interleaved q, qd) becomes env k's DOF state; None: the wrapper's own
+        `_dof_state` as the caller edited it"""
+        self._scatter("dof", state)
+
+    def set_actor_root_state_tensor(self, state=None) -> None:
+        """gym.set_actor_root_state_tensor: row k of `state` [K, A, 13] becomes env k's root state; None: the wrapper's own
+        `_root_state` as the caller edited it.  Rows of fixed actors must equal the shared state (ValueError otherwise)"""
+        self._scatter("root", state)
+
+    def set_dof_state_tensor_indexed(self, state, env_ids) -> None:
+        """row j of `state` [len(env_ids), 2n] becomes the DOF state of env env_ids[j]; the other envs stay as they are"""
+        self._scatter("dof", state, env_ids)
+
+    def set_actor_root_state_tensor_indexed(self, state, env_ids) -> None:
+        """row j of `state` [len(env_ids), A, 13] becomes the root state of env env_ids[j]; the other envs stay as they are"""
+        self._scatter("root", state, env_ids)
+
+    def reset_envs(self, env_ids) -> None:
+        """episodic reset: the listed envs return to the state every env starts a rollout from (the last single state pushed); the
+        other envs go on from where they are"""
+        ids = self._env_ids(env_ids)
+        self._reset_envs_if_needed()
+        capi.check(self._lib, self._lib.mppi_sim_reset_indexed(self._ctx, _dev_ptr(ids), int(ids.numel())))
+        self._stale = True
 
     def draw_lines(self, lines) -> None:
         """viewer call of the reference's world scripts: there is no viewer here; accepted and ignored"""
