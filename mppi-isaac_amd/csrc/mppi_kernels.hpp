@@ -466,6 +466,12 @@ __global__ __launch_bounds__(LAY == 8 ? 2 * kWave : kWave) void k_rollout_quad(c
                                                         unsigned long long *__restrict__ wave_clk, float *__restrict__ traj = nullptr) {
 #if defined(__HIP_DEVICE_COMPILE__)  // (the host pass sees the 4-float emulation type of mppi_quad.hpp)
     const unsigned long long clk0 = wave_clk != nullptr ? wall_clock64() : 0ull;
+    // LAY = 8: ONE wavefront per SIMD, whatever the register count of this build.  The host selects the octet kernel up to one
+    // wavefront per SIMD (K = 8192 on the MI355X) and counts on each having a SIMD to itself; that used to follow from the kernel's
+    // 256 + 1 registers and no longer does (254 with the joint vectors: two fit a SIMD, the dispatcher pairs them while other SIMDs
+    // idle - measured at K = 8192: 7740 -> 5810 Hz).  As in k_rollout_oct_pair: naming a high AGPR as clobbered puts the allocation
+    // above half the register file; no instruction is issued for it.
+    if constexpr (LAY == 8) asm volatile("; one wavefront per SIMD" ::: "a31");
     // (LAY = 8: a workgroup is TWO wavefronts of eight samples each - 16 consecutive samples, one record, one staged model)
     const auto [lm, sc, s_lin] = rollout_prologue<T, (LAY == 8 ? 2 * kWave : kWave), LAY == 8>(m, cfg, cost, x0_root, U);
     const int chunk = xcd_chunk();   // 16 samples either way
@@ -478,7 +484,8 @@ __global__ __launch_bounds__(LAY == 8 ? 2 * kWave : kWave) void k_rollout_quad(c
         // one wave-uniform branch picks the instruction stream specialised for an all-revolute tree
         if constexpr (LAY == 8) {
             const OctAba ab{oct_bodies(&lm.b[0], s_lin), oct_lane()};
-            if (((CModel *)m)->all_revolute) s = quad_rollout<T, 0, DUMP>(lm, *(CCfg *)cfg, *(CCost *)cost, sc, x0_dof, x0_root, eps, prior, du, viz, k, leader, quad_row(), lane4 < 3, traj, ab);
+            // (all-revolute trees: the per-joint scalars one joint per lane, mppi_oct.hpp OctAbaJv)
+            if (((CModel *)m)->all_revolute) s = quad_rollout<T, 0, DUMP>(lm, *(CCfg *)cfg, *(CCost *)cost, sc, x0_dof, x0_root, eps, prior, du, viz, k, leader, quad_row(), lane4 < 3, traj, oct_joint_vectors<T>(ab, lm));
             else s = quad_rollout<T, -1, DUMP>(lm, *(CCfg *)cfg, *(CCost *)cost, sc, x0_dof, x0_root, eps, prior, du, viz, k, leader, quad_row(), lane4 < 3, traj, ab);
         } else {
             if (((CModel *)m)->all_revolute) s = quad_rollout<T, 0, DUMP>(lm, *(CCfg *)cfg, *(CCost *)cost, sc, x0_dof, x0_root, eps, prior, du, viz, k, leader, quad_row(), lane4 < 3, traj);
@@ -592,7 +599,8 @@ __global__ __launch_bounds__(4 * kWave) void k_rollout_oct_pair(const DevModel *
     if (!helper) {
         // one wave-uniform branch picks the instruction stream specialised for an all-revolute tree
         const OctAba ab{oct_bodies(&lm.b[0], s_lin), oct_lane()};
-        if (((CModel *)m)->all_revolute) pair_owner<T, 0>(lm, *(CCfg *)cfg, *(CCost *)cost, x0_dof, x0_root, urow, xa, xb, 2 * kWave, want_viz, ab);
+        // (all-revolute trees: the per-joint scalars one joint per lane, mppi_oct.hpp OctAbaJv)
+        if (((CModel *)m)->all_revolute) pair_owner<T, 0>(lm, *(CCfg *)cfg, *(CCost *)cost, x0_dof, x0_root, urow, xa, xb, 2 * kWave, want_viz, oct_joint_vectors<T>(ab, lm));
         else pair_owner<T, -1>(lm, *(CCfg *)cfg, *(CCost *)cost, x0_dof, x0_root, urow, xa, xb, 2 * kWave, want_viz, ab);
     } else {
         s = pair_helper<T>(lm, *(CCfg *)cfg, *(CCost *)cost, sc, eps, prior, du, viz, ke, quad_row(), urow, xa, xb, 2 * kWave);

@@ -166,6 +166,48 @@ __device__ __forceinline__ void opass1_root_fused(OF p, OF az, OF qd, OF &S, OF 
         : [p] "v"(p), [az] "v"(az), [qd] "v"(qd));
 }
 
+// ... the same two blocks with qd taken from a JOINT VECTOR (OctAbaJv below): QD holds joint 4v + r in lane r of both quads, and
+// the two products with qd read it as their DPP source, quad_perm:[r,r,r,r] - a broadcast that costs no instruction.  QD was
+// written by the integration of the previous substep, long before; MPPI_LEAD as for every block whose first slots read through DPP
+#define MPPI_BR "quad_perm:[%[r],%[r],%[r],%[r]] row_mask:0xf bank_mask:0xf bound_ctrl:1"
+template <int R>
+__device__ __forceinline__ void opass1_fused_jv(OF p, OF az, OF QD, OF vp, OF wp, OF lin, OF &S, OF &v, OF &w, OF &cb) {
+    OF saz, t, Z, sj, tc;
+    asm(MPPI_LEAD
+        "v_mov_b32 %[S], %[az]\n\t"                               //  1 S   = az
+        "v_mul_f32_dpp %[saz], %[QD], %[az] " MPPI_BR "\n\t"       //  2 saz = qd az
+        "v_mul_f32_dpp %[t], %[az], %[p] " MPPI_R1 "\n\t"         //  3 t   = rot1(az) p
+        "v_fmac_f32_dpp %[t], %[p], -%[az] " MPPI_R1 "\n\t"       //  4 t  -= rot1(p) az
+        "v_mul_f32 %[Z], %[lin], %[vp]\n\t"                       //  5 Z   = lin vp
+        "v_add_f32 %[w], %[wp], %[saz]\n\t"                       //  6 w   = wp + saz
+        "v_mov_b32_dpp %[S], %[t] quad_perm:[1,2,0,1] row_mask:0xf bank_mask:0xc\n\t"   //  7 S (linear lanes) = rot1(t)     (t written at 4)
+        "v_mul_f32_dpp %[sj], %[QD], %[S] " MPPI_BR "\n\t"         //  8 sj  = qd S
+        "v_add_f32 %[v], %[vp], %[sj]\n\t"                        //  9 v   = vp + sj
+        "v_mul_f32_dpp %[tc], %[saz], %[Z] " MPPI_R1 "\n\t"       // 10 tc  = rot1(saz) Z    (saz written at 2)
+        "v_fmac_f32_dpp %[tc], %[Z], -%[saz] " MPPI_R1 "\n\t"     // 11 tc -= rot1(Z) saz    (Z written at 5)
+        "v_fmac_f32_dpp %[tc], %[sj], %[wp] " MPPI_R1 "\n\t"      // 12 tc += rot1(sj) wp    (sj written at 8)
+        "v_fmac_f32_dpp %[tc], %[wp], -%[sj] " MPPI_R1 "\n\t"     // 13 tc -= rot1(wp) sj
+        "s_nop 1\n\t"                                             // 14                      (tc written at 13)
+        "v_mov_b32_dpp %[cb], %[tc] " MPPI_R1                     // 15 cb  = rot1(tc)
+        : [S] "=&v"(S), [v] "=&v"(v), [w] "=&v"(w), [cb] "=&v"(cb), [saz] "=&v"(saz), [t] "=&v"(t), [Z] "=&v"(Z), [sj] "=&v"(sj), [tc] "=&v"(tc)
+        : [p] "v"(p), [az] "v"(az), [QD] "v"(QD), [vp] "v"(vp), [wp] "v"(wp), [lin] "v"(lin), [r] "i"(R));
+}
+template <int R>
+__device__ __forceinline__ void opass1_root_fused_jv(OF p, OF az, OF QD, OF &S, OF &v, OF &w) {
+    OF t;
+    asm(MPPI_LEAD
+        "v_mov_b32 %[S], %[az]\n\t"                               //  1 S   = az
+        "v_mul_f32_dpp %[w], %[QD], %[az] " MPPI_BR "\n\t"         //  2 w   = qd az
+        "v_mul_f32_dpp %[t], %[az], %[p] " MPPI_R1 "\n\t"         //  3 t   = rot1(az) p
+        "v_fmac_f32_dpp %[t], %[p], -%[az] " MPPI_R1 "\n\t"       //  4 t  -= rot1(p) az
+        "s_nop 1\n\t"                                             //  5                      (t written at 4)
+        "v_mov_b32_dpp %[S], %[t] quad_perm:[1,2,0,1] row_mask:0xf bank_mask:0xc\n\t"   //  6 S (linear lanes) = rot1(t)
+        "v_mul_f32_dpp %[v], %[QD], %[S] " MPPI_BR                //  7 v   = qd S
+        : [S] "=&v"(S), [v] "=&v"(v), [w] "=&v"(w), [t] "=&v"(t)
+        : [p] "v"(p), [az] "v"(az), [QD] "v"(QD), [r] "i"(R));
+}
+#undef MPPI_BR
+
 // ---- inward pass of one body -----------------------------------------------------------------------------------------------------------
 // in:  Tr = R Ic rows and h = m c from qmoments (both halves; the linear lanes' view of the inertia block has Ic = 0, 1/m = 0),
 //      R0..R2 = columns of R, v / w spatial / angular velocity, S, cb, kdh, tau; INNER bodies: the children's articulated inertia
@@ -349,7 +391,8 @@ __device__ __forceinline__ void ooutward_fused_check(OF W, OF ap, OF cb, OF S, O
 // zero in the other without a select.  tau / kdh / qd / qdd: replicated scalars (same in all eight lanes of a sample).
 // CHECK: the drive-limit test of quad_step rides in the wait slots of the outward pass (ooutward_fused_check): tt[i] = tau_exp[i] -
 // kdh[i] qdd[i] and excess = max_i(|tt[i]| - effort_i) come back with the accelerations
-template <class T, bool CHECK = false, class BP, class M, int JT>
+// JV: qd is an array of JOINT VECTORS (OctAbaJv below; all-revolute trees) - everything else as above
+template <class T, bool CHECK = false, bool JV = false, class BP, class M, int JT>
 __device__ __forceinline__ void oct_aba(M &m, BP bodies, const OctLane &ol, const QPose<T, JT> &P, const OF *qd, const OF *tau_exp, const OF *kdh, OF *qdd,
                                         JointLimits *lim, OF *tt = nullptr, OF *excess_out = nullptr) {
     constexpr int NB = T::NB;
@@ -365,12 +408,14 @@ __device__ __forceinline__ void oct_aba(M &m, BP bodies, const OctLane &ol, cons
         const OF az = P.R2p[i].x;
         if (P.revolute(i)) {
             if constexpr (par < 0) {
-                opass1_root_fused(P.pos(i), az, qd[i], S[i], v[i], w[i]);
+                if constexpr (JV) opass1_root_fused_jv<i & 3>(P.pos(i), az, qd[i >> 2], S[i], v[i], w[i]);
+                else opass1_root_fused(P.pos(i), az, qd[i], S[i], v[i], w[i]);
                 cb[i] = zero;
             } else {
-                opass1_fused(P.pos(i), az, qd[i], v[pj], w[pj], ol.lin, S[i], v[i], w[i], cb[i]);
+                if constexpr (JV) opass1_fused_jv<i & 3>(P.pos(i), az, qd[i >> 2], v[pj], w[pj], ol.lin, S[i], v[i], w[i], cb[i]);
+                else opass1_fused(P.pos(i), az, qd[i], v[pj], w[pj], ol.lin, S[i], v[i], w[i], cb[i]);
             }
-        } else {  // prismatic: S = (0 | az), no angular velocity of its own; c = vp x (qd S) = (0 | wp x qd az)
+        } else if constexpr (!JV) {  // prismatic: S = (0 | az), no angular velocity of its own; c = vp x (qd S) = (0 | wp x qd az)
             S[i] = ol.lin * az;
             const OF sj = qd[i] * S[i];
             if constexpr (par < 0) {
@@ -461,6 +506,7 @@ struct OctAba {
     OctBodies bodies;
     OctLane ol;
     static constexpr bool kFusedLimitCheck = true;
+    static constexpr bool kJointVectors = false;
     template <class T, class M, int JT>
     __device__ __forceinline__ void aba(M &m, const QPose<T, JT> &P, const QF *qd, const QF *tau_exp, const QF *kdh, QF *qdd, JointLimits *lim) const {
         oct_aba<T>(m, bodies, ol, P, qd, tau_exp, kdh, qdd, lim);
@@ -472,6 +518,168 @@ struct OctAba {
         oct_aba<T, true>(m, bodies, ol, P, qd, tau_exp, kdh, qdd, lim, tt, &excess);
     }
 };
+
+// ---- joint vectors: the per-joint scalars of a step, ONE JOINT PER LANE -------------------------------------------------------------
+// quad_step (mppi_quad.hpp) holds q, qd, the drive target and torque, the joint range and vmax as replicated scalars: every line of
+// the drive, the integration (two bounds, four med3), 1/h and sin / cos is issued once per joint with the same value in all eight
+// lanes of the sample - 108 of the 1002 instructions of the panda's substep loop, 14 of them transcendentals.  Here they are
+// JOINT VECTORS in the TWO-VECTOR layout: register v holds joint 4v + r in lane r (= lane & 3) of BOTH quads of the sample, so
+// every such line is issued (NB + 3) / 4 times (panda: 2 instead of 7).  Lanes without a joint (pad lanes) START at q = qd = 0
+// with limits -inf / +inf and vmax = +inf; gather() leaves the vector's first joint's value in them (its acceleration, its
+// command), so from the first substep on a pad lane integrates a phantom joint without bounds.  Whatever it holds is never
+// broadcast and never stored: no joint<I>, no opass1 block and no dump names a pad lane.  What the solve needs replicated:
+//   qd        free - the DPP source of its two products in pass 1 (opass1_fused_jv)
+//   tau       one v_mov_b32_dpp per joint (quad_perm:[r,r,r,r]; bit-identical in all eight lanes: both quads hold the same vector)
+//   cos, sin  two per joint, into the register pair the packed kinematics read (quad_fk_from_sc)
+// and the accelerations come back with one select per joint (three lane masks, lane & 3 = 1, 2, 3).  Counted for the panda:
+// drive 4 + 7, gather 5, integration 20, sin / cos 6 + 14 = 56 against 108; the range, vmax and 1/h are per-launch constants of
+// the policy object.  Same operations on the same operands in the same order per joint: the results are the replicated form's,
+// bit for bit (tests/test_gpu_lane_scalars.py).  All-revolute trees only (JT = 0); trees with prismatic joints and the position
+// drive keep the replicated form.
+template <class T>
+struct OctSinCos {  // sin q, cos q per joint vector; the kinematics take joint I's pair as two broadcasts
+    OF sn[(T::NB + 3) / 4], cn[(T::NB + 3) / 4];
+    template <int I>
+    __device__ __forceinline__ void get(OF &s, OF &c) const {
+        c = bc<I & 3>(cn[I >> 2]);
+        s = bc<I & 3>(sn[I >> 2]);
+    }
+};
+template <class T>
+struct OctAbaJv : OctAba {
+    static constexpr bool kJointVectors = true;
+    static constexpr int NB = T::NB, NV = (NB + 3) / 4;
+    static_assert(NB <= kMaxNu, "joint vectors: targets_identity reads u[0 .. NB)");
+    OF lo[NV], hi[NV], vmax[NV];   // joint range and velocity limit, built once per launch from the staged model
+    float inv_h;                   // 1 / h with its Newton step, as quad_step takes it every substep
+    int r;                         // lane & 3: the joint of a vector this lane holds
+    template <class M>
+    __device__ __forceinline__ OctAbaJv(const OctAba &ab, M &m) : OctAba(ab) {
+        r = (int)(threadIdx.x & 3u);
+        inv_h = frcp(m.h);
+#pragma unroll
+        for (int v = 0; v < NV; v++) {
+            const int j = 4 * v + r;
+            const bool on = j < NB;
+            const int jj = on ? j : 0;
+            lo[v] = on ? m.b[jj].k0.lower : -INFINITY;
+            hi[v] = on ? m.b[jj].k0.upper : INFINITY;
+            vmax[v] = on ? m.b[jj].k1.vmax : INFINITY;
+        }
+    }
+    // lane r of vector v := x[4v + r] (x: replicated per joint): three selects per vector
+    template <class X>
+    __device__ __forceinline__ void gather(const X *x, OF *out) const {
+        static_for<0, NV>([&](auto vc) MPPI_LAMBDA {   // (compile-time indices: x stays in registers)
+            constexpr int v = vc;
+            OF g = x[4 * v];
+            static_for<1, 4>([&](auto kc) MPPI_LAMBDA {
+                constexpr int k = kc;
+                if constexpr (4 * v + k < NB) {
+                    OF xk = x[4 * v + k];
+                    asm("" : "+v"(xk));   // (a value, not a load: "select of loads" would become a load through a selected address)
+                    g = r == k ? xk : g;
+                }
+            });
+            out[v] = g;
+        });
+    }
+    template <int I>
+    __device__ __forceinline__ OF joint(const OF *x) const { return bc<I & 3>(x[I >> 2]); }   // joint I's scalar, replicated
+    __device__ __forceinline__ void load_state(const float *dof0, OF *q, OF *qd) const {
+#pragma unroll
+        for (int v = 0; v < NV; v++) {
+            const int j = 4 * v + r;
+            const bool on = j < NB;
+            q[v] = on ? dof0[2 * (on ? j : 0)] : 0.f;
+            qd[v] = on ? dof0[2 * (on ? j : 0) + 1] : 0.f;
+        }
+    }
+    template <class TT>
+    __device__ __forceinline__ void fk_from(const BodyK0 *blk, const OF *q, QPose<TT, 0> &P) const {
+        OctSinCos<T> sc;
+#pragma unroll
+        for (int v = 0; v < NV; v++) qsincos(q[v], sc.sn[v], sc.cn[v]);
+        quad_fk_from_sc<T, 0>(blk, (const OF *)nullptr, P, sc);
+    }
+    template <class TT, class M>
+    __device__ __forceinline__ void fk(M &m, const OF *q, QPose<TT, 0> &P) const {
+        BodyK0 blk[NB ? NB : 1];
+        quad_fk_blocks<T>(m, blk);
+        fk_from<TT>(blk, q, P);
+    }
+    // the drive targets of a horizon step: the identity map (one unit-gain command per body) ...
+    __device__ __forceinline__ void targets_identity(const float *u, OF *target) const { gather(u, target); }
+    // ... and the general map, formed per lane from the lane's own row of the command map (the sum in quad_rollout's order)
+    template <int MAXC, class M>
+    __device__ __forceinline__ void targets_mapped(M &m, const float *u, OF *target) const {
+#pragma unroll
+        for (int v = 0; v < NV; v++) {
+            const int j = 4 * v + r;
+            const CmdBlock b = load_block<CmdBlock>(m.b[j < NB ? j : 0].cmd);
+            float tg = 0.f;
+#pragma unroll
+            for (int c = 0; c < MAXC; c++) tg += b.v[c] * u[c];
+            target[v] = tg;
+        }
+    }
+    // trajectory dump: lane r stores its own joint (the two quads of a sample store the same value to the same address)
+    __device__ __forceinline__ void dump(const OF *q, const OF *qd, float *traj, unsigned HK, unsigned col) const {
+#pragma unroll
+        for (int v = 0; v < NV; v++) {
+            const int j = 4 * v + r;
+            if (j < NB) {
+                traj[(unsigned)j * HK + col] = q[v];
+                traj[(unsigned)(NB + j) * HK + col] = qd[v];
+            }
+        }
+    }
+    // One simulator step, quad_step's (mppi_quad.hpp) for an all-revolute tree in velocity or effort mode: Q, QD, TGT joint vectors.
+    // The substep restates quad_step's - the drive, the limit test, the second solve (octet layout: no shift of the origin) - on
+    // joint vectors; the integration is the shared quad_integrate.  A change to quad_step's substep belongs here too.
+    template <class TT, class M>
+    __device__ __forceinline__ void step(M &m0, QPose<TT, 0> &P, OF *Q, OF *QD, const OF *TGT) const {
+        M *mp = &m0;
+        for (int s = 0; s < m0.substeps; s++) {
+            M &m = *launder(mp);
+            const float h = m.h, kd = m.kd;
+            OF TAU[NV], QDD[NV], tau[NB], kdh[NB], qdd[NB], tt[NB];
+            JointLimits lim[NB];
+            if (m.drive_mode == kDriveVelocity) {
+#pragma unroll
+                for (int v = 0; v < NV; v++) TAU[v] = kd * (TGT[v] - QD[v]);
+            } else {
+#pragma unroll
+                for (int v = 0; v < NV; v++) TAU[v] = TGT[v] - kd * QD[v];
+            }
+            static_for<0, NB>([&](auto ic) MPPI_LAMBDA { tau[ic] = joint<ic>(TAU); });
+            const OF kdhq = kd * h;
+            static_for<0, NB>([&](auto ic) MPPI_LAMBDA { kdh[ic] = kdhq; });
+            OF excess = -INFINITY;
+            oct_aba<T, true, true>(m, bodies, ol, P, QD, tau, kdh, qdd, lim, tt, &excess);
+            if (qany_gt(excess, 0.f)) {   // a drive beyond its effort limit (rare): held at the bound, solved again - quad_step
+                static_for<0, NB>([&](auto ic) MPPI_LAMBDA {
+                    constexpr int i = ic;
+                    const OF eff = lim[i].effort;
+                    const bool sat = qany_gt(qabs(tt[i]), eff);
+                    tau[i] = sat ? qwhere_gt(tt[i], 0.f, eff, -eff) : tau[i];
+                    kdh[i] = sat ? 0.f : kdh[i];
+                });
+                oct_aba<T, false, true>(*launder(mp), bodies, ol, P, QD, tau, kdh, qdd, lim);
+            }
+            // the kinematic blocks of the NEXT pose: their round trip runs under the integration's arithmetic
+            BodyK0 blk0[NB];
+            quad_fk_blocks<T>(*launder(mp), blk0);
+            gather(qdd, QDD);
+#pragma unroll
+            for (int v = 0; v < NV; v++) quad_integrate(Q[v], QD[v], QDD[v], h, inv_h, lo[v], hi[v], vmax[v]);   // once per vector
+            fk_from<TT>(blk0, Q, P);
+        }
+    }
+};
+// the joint-vector form of a policy where the tree allows it (the caller has picked the all-revolute instantiation)
+template <class T, class M>
+__device__ __forceinline__ OctAbaJv<T> oct_joint_vectors(const OctAba &ab, M &m) { return OctAbaJv<T>(ab, m); }
 
 // the linear lanes' view of a body's inertia block: inertia tensor and 1/m zero, everything else as it is
 __device__ __forceinline__ BodyK1 oct_lin_view(const BodyK1 &b) {

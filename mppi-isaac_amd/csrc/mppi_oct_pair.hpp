@@ -44,29 +44,47 @@ __device__ __forceinline__ void pair_owner(M &m0, CCfg &cfg0, CCost &cost0, cons
     const int H = cfg0.H, kind = cost0.kind, link = cost0.link[0], viz_link = cfg0.viz_link;
     const bool cmd_identity = m0.cmd_identity != 0, need_link = kind == kCostPandaReach, point = kind == kCostPointReach;
     const bool own_viz = want_viz && (viz_link != link || !need_link);
-    QF q[NB], qd[NB], target[NB];
-    static_for<0, NB>([&](auto ic) MPPI_LAMBDA {
-        constexpr int i = ic;
-        q[i] = qrep(dof0[2 * i]);
-        qd[i] = qrep(dof0[2 * i + 1]);
-    });
+    constexpr bool JV = AB::kJointVectors;     // (mppi_oct.hpp OctAbaJv: joint 4v + r in lane r of register v)
+    constexpr int NS = JV ? (NB + 3) / 4 : NB;
+    static_assert(!JV || (NS * 4 <= kStride && NB == MAXC), "joint vectors: the table row holds a word per lane of every vector");
+    QF q[NS], qd[NS], target[NS];
+    if constexpr (JV) {
+        ab.load_state(dof0, q, qd);
+    } else {
+        static_for<0, NB>([&](auto ic) MPPI_LAMBDA {
+            constexpr int i = ic;
+            q[i] = qrep(dof0[2 * i]);
+            qd[i] = qrep(dof0[2 * i + 1]);
+        });
+    }
     QPose<T, JT> P;  // forward kinematics of the current q, carried across the whole horizon
     quad_base<T>(m0, root, P);
-    quad_fk<T>(m0, q, P);
+    if constexpr (JV) ab.template fk<T>(m0, q, P);
+    else quad_fk<T>(m0, q, P);
     M *mp = &m0;
     MPPI_BARRIER(10);
     for (int t = 0; t < H; t++) {
         float u[kMaxNu];
 #pragma unroll
         for (int c = MAXC; c < kMaxNu; c++) u[c] = 0.f;
+        if (!JV || !cmd_identity) {
 #pragma unroll
-        for (int j = 0; j < kStride / 4; j++) {
-            const f32x4 v = *reinterpret_cast<const LF4 *>(urow + t * kRow + 4 * j);
+            for (int j = 0; j < kStride / 4; j++) {
+                const f32x4 v = *reinterpret_cast<const LF4 *>(urow + t * kRow + 4 * j);
 #pragma unroll
-            for (int c = 0; c < 4; c++)
-                if (4 * j + c < MAXC) u[4 * j + c] = v[c];
+                for (int c = 0; c < 4; c++)
+                    if (4 * j + c < MAXC) u[4 * j + c] = v[c];
+            }
         }
-        if (cmd_identity) {  // fixed-base arms, the point robot: one unit-gain command per body
+        if constexpr (JV) {
+            // joint vectors: this lane's joint's entry of the row, one 4-byte read per vector (the helpers write zeros beyond nu)
+            if (cmd_identity) {
+#pragma unroll
+                for (int v = 0; v < NS; v++) target[v] = urow[t * kRow + 4 * v + ab.r];
+            } else {
+                ab.template targets_mapped<MAXC>(*launder(mp), u, target);
+            }
+        } else if (cmd_identity) {  // fixed-base arms, the point robot: one unit-gain command per body
             static_for<0, NB>([&](auto ic) MPPI_LAMBDA { target[ic] = qrep(u[ic < kMaxNu ? (int)ic : 0]); });
         } else {
             M &m = *launder(mp);
@@ -87,7 +105,8 @@ __device__ __forceinline__ void pair_owner(M &m0, CCfg &cfg0, CCost &cost0, cons
             quad_link_body_pose<T>(*launder(mp), P, link, Rb, pb);
             xa[s] = f32x4{Rb.c[0], Rb.c[1], Rb.c[2], pb};
         } else if (point) {
-            xa[s] = f32x4{q[0], q[NB > 1 ? 1 : 0], 0.f, 0.f};
+            if constexpr (JV) xa[s] = f32x4{ab.template joint<0>(q), ab.template joint<(NB > 1 ? 1 : 0)>(q), 0.f, 0.f};
+            else xa[s] = f32x4{q[0], q[NB > 1 ? 1 : 0], 0.f, 0.f};
         }
         if (own_viz) {
             QM3 Rb;

@@ -447,6 +447,15 @@ MPPI_HD void quad_fk_blocks(M &m, BodyK0 *blk) {
 }
 template <class T, int JT>
 MPPI_HD void quad_fk_from(const BodyK0 *blk, const QF *q, QPose<T, JT> &P);
+// where the kinematics take (sin q_i, cos q_i) from: here from the replicated position of joint i; the octet layout's joint
+// vectors (mppi_oct.hpp OctSinCos) take them once per VECTOR of four joints and hand out broadcasts
+struct QuadSinCos {
+    const QF *q;
+    template <int I>
+    MPPI_HD void get(QF &s, QF &c) const { qsincos(q[I], s, c); }
+};
+template <class T, int JT, class SC>
+MPPI_HD void quad_fk_from_sc(const BodyK0 *blk, const QF *q, QPose<T, JT> &P, const SC &sincos);
 template <class T, class M, int JT>
 MPPI_HD void quad_fk(M &m, const QF *q, QPose<T, JT> &P) {
     BodyK0 blk[T::NB ? T::NB : 1];
@@ -455,6 +464,10 @@ MPPI_HD void quad_fk(M &m, const QF *q, QPose<T, JT> &P) {
 }
 template <class T, int JT>
 MPPI_HD void quad_fk_from(const BodyK0 *blk, const QF *q, QPose<T, JT> &P) {
+    quad_fk_from_sc<T, JT>(blk, q, P, QuadSinCos{q});
+}
+template <class T, int JT, class SC>
+MPPI_HD void quad_fk_from_sc(const BodyK0 *blk, const QF *q, QPose<T, JT> &P, const SC &sincos) {
     static_for<0, T::NB>([&](auto ic) MPPI_LAMBDA {
         constexpr int i = ic;
         constexpr int par = T::par[i];
@@ -463,7 +476,7 @@ MPPI_HD void quad_fk_from(const BodyK0 *blk, const QF *q, QPose<T, JT> &P) {
         const QF2 Rp01 = par < 0 ? P.Rb01 : P.R01[par < 0 ? 0 : par], Rp2p = par < 0 ? P.Rb2p : P.R2p[par < 0 ? 0 : par];
         const bool rev = JT == 0 || b.jtype == 0;
         QF sn = qrep(0.f), cn = qrep(1.f);  // prismatic: the identity rotation
-        if (rev) qsincos(q[i], sn, cn);
+        if (rev) sincos.template get<i>(sn, cn);
         QF2 R01, RT2p;  // columns 0, 1 of R_parent Rt Rz(q) | column 2 and R_parent pt
 #if defined(MPPI_DPP_FMAC) && !defined(MPPI_NO_PK_FK)
         // six packed multiply-adds for the twelve products-and-sums of [R_parent Rt | R_parent pt] - the parent's column k is
@@ -671,6 +684,7 @@ MPPI_HD void quad_aba(M &m, const QPose<T, JT> &P, const QF *qd, const QF *tau_e
 // sample per two quads) - the step / rollout code around the solve is the same for both.
 struct QuadAba {
     static constexpr bool kFusedLimitCheck = false;
+    static constexpr bool kJointVectors = false;   // q, qd, target: one replicated register per joint
     template <class T, class M, int JT>
     MPPI_HD void aba(M &m, const QPose<T, JT> &P, const QF *qd, const QF *tau_exp, const QF *kdh, QF *qdd, JointLimits *lim) const {
         quad_aba<T>(m, P, qd, tau_exp, kdh, qdd, lim);
@@ -687,12 +701,34 @@ MPPI_HD void quad_base(M &m, const float *root, QPose<T, JT> &P) {
     P.set_base(Rb, qsel(rs[0], rs[1], rs[2]));
 }
 
+// The integration of ONE joint register over a substep (replicated scalars here; a joint vector in mppi_oct.hpp OctAbaJv::step - the
+// one place the line lives, so the two forms cannot drift apart): semi-implicit Euler with the velocity limit and the inelastic
+// stops as ONE pair of bounds (absent limits are +-inf, mppi_pack.hpp: no branches).  joint_limit() of mppi_device.hpp says: at a
+// stop the velocity becomes the displacement that happened, ve = (limit - x_old) / h, never pointing back out of the range.
+// x_old + h v < lo is the same as v < ve_lo, so the stop is the unconditional bound v >= min(ve_lo, 0) - and the two clamps compose
+// into one because both intervals contain 0: v in [med3(ve_lo, -vmax, 0), med3(ve_hi, 0, vmax)]
+MPPI_HD void quad_integrate(QF &q, QF &qd, QF qdd, float h, float inv_h, QF lo, QF hi, QF vmax) {
+    const QF z = qrep(0.f);
+    QF v = qd + h * qdd;
+    const QF vlo = qclamp((lo - q) * inv_h, -vmax, z), vhi = qclamp((hi - q) * inv_h, z, vmax);
+    v = qclamp(v, vlo, vhi);
+    q = qclamp(q + h * v, lo, hi);
+    qd = v;
+}
+
 // One simulator step.  P must hold the forward kinematics of q on entry (base pose included) and holds the
 // forward kinematics of the NEW q on exit: the pose computed for the cost / next step is never recomputed.
 template <class T, class M, int JT, class AB = QuadAba>
 MPPI_HD void quad_step(M &m0, QPose<T, JT> &P, QF *q, QF *qd, const QF *target, const AB &ab = AB{}) {
     constexpr int NB = T::NB;
     M *mp = &m0;
+    if constexpr (AB::kJointVectors) {   // (octet layout, all-revolute trees: q, qd, target are joint vectors, mppi_oct.hpp OctAbaJv)
+        // (OctAbaJv::step restates the substep below - drive, limit test, second solve - on joint vectors and shares
+        // quad_integrate: a change to the substep here belongs there too; tests/test_gpu_lane_scalars.py pins both to one result)
+        static_assert(JT == 0, "joint vectors: the all-revolute specialisation");
+        ab.template step<T>(m0, P, q, qd, target);
+        return;
+    }
     // position mode (isaacgym_wrapper.py:571-572): apply_robot_cmd overwrites the DOF state with the command.  It lives in the
     // GENERIC instantiation only (JT != 0; mppi_pack.hpp clears all_revolute for a position-driven robot): the all-revolute
     // specialisation is the metric's instruction stream and carries no trace of it (measured: as a run-time branch of the
@@ -770,22 +806,7 @@ MPPI_HD void quad_step(M &m0, QPose<T, JT> &P, QF *q, QF *qd, const QF *target, 
         quad_fk_blocks<T>(*launder(mp), blk0);
         static_for<0, NB>([&](auto ic) MPPI_LAMBDA {
             constexpr int i = ic;
-            const JointLimits b = lim[i];
-            QF v = qd[i] + h * qdd[i];
-            QF x;
-            {
-                // velocity limit and inelastic stops as ONE pair of bounds (absent limits are +-inf, mppi_pack.hpp: no branches).
-                // joint_limit() of mppi_device.hpp says: at a stop the velocity becomes the displacement that happened,
-                // ve = (limit - x_old) / h, never pointing back out of the range.  x_old + h v < lo is the same as v < ve_lo, so
-                // the stop is the unconditional bound v >= min(ve_lo, 0) - and the two clamps compose into one because both
-                // intervals contain 0: v in [med3(ve_lo, -vmax, 0), med3(ve_hi, 0, vmax)]
-                const QF lo = qrep(blk0[i].lower), hi = qrep(blk0[i].upper), z = qrep(0.f);  // (absent: -inf, +inf)
-                const QF vlo = qclamp((lo - q[i]) * inv_h, qrep(-b.vmax), z), vhi = qclamp((hi - q[i]) * inv_h, z, qrep(b.vmax));
-                v = qclamp(v, vlo, vhi);
-                x = qclamp(q[i] + h * v, lo, hi);
-            }
-            q[i] = x;
-            qd[i] = v;
+            quad_integrate(q[i], qd[i], qdd[i], h, inv_h, qrep(blk0[i].lower), qrep(blk0[i].upper), qrep(lim[i].vmax));  // (absent: -inf, +inf)
         });
         quad_fk_from<T, JT>(blk0, q, P);
     }
@@ -970,17 +991,24 @@ MPPI_HD QF quad_rollout(M &m0, CCfg &cfg0, CCost &cost0, LStep &sc, const float 
     const bool special_here = is_null || is_prior;
 #endif
     const bool plain_controls = !special_here && nu == MAXC && !abs_cost;
-    QF q[NB], qd[NB], target[NB];
-    static_for<0, NB>([&](auto ic) MPPI_LAMBDA {
-        constexpr int i = ic;
-        q[i] = qrep(dof0[2 * i]);
-        qd[i] = qrep(dof0[2 * i + 1]);
-    });
+    constexpr bool JV = AB::kJointVectors;     // (mppi_oct.hpp OctAbaJv: joint 4v + r in lane r of register v)
+    constexpr int NS = JV ? (NB + 3) / 4 : NB;
+    QF q[NS], qd[NS], target[NS];
+    if constexpr (JV) {
+        ab.load_state(dof0, q, qd);
+    } else {
+        static_for<0, NB>([&](auto ic) MPPI_LAMBDA {
+            constexpr int i = ic;
+            q[i] = qrep(dof0[2 * i]);
+            qd[i] = qrep(dof0[2 * i + 1]);
+        });
+    }
     QF S = qrep(0.f);
     float ctrl = 0.f, disc = 1.f;
     QPose<T, JT> P;  // forward kinematics of the current q, carried across the whole horizon
     quad_base<T>(m0, root, P);
-    quad_fk<T>(m0, q, P);
+    if constexpr (JV) ab.template fk<T>(m0, q, P);
+    else quad_fk<T>(m0, q, P);
     M *mp = &m0;
     for (int t = 0; t < H; t++) {
         float u[kMaxNu];
@@ -988,7 +1016,10 @@ MPPI_HD QF quad_rollout(M &m0, CCfg &cfg0, CCost &cost0, LStep &sc, const float 
                                : apply_controls_q<MAXC, false>(sc, lambda, abs_cost, nu, K, rows, t, k, is_null, is_prior, leader, du, u);
         // next step's rows are requested now and consumed after this step's dynamics (the last request re-reads row H-1)
         load_controls_q<MAXC>(sc, eps, prior, nu, K, t + 1 < H ? t + 1 : t, k, rows);
-        if (cmd_identity) {  // fixed-base arms, the point robot: one unit-gain command per body
+        if constexpr (JV) {
+            if (cmd_identity) ab.targets_identity(u, target);
+            else ab.template targets_mapped<MAXC>(*launder(mp), u, target);
+        } else if (cmd_identity) {  // fixed-base arms, the point robot: one unit-gain command per body
             static_for<0, NB>([&](auto ic) MPPI_LAMBDA { target[ic] = qrep(u[ic < kMaxNu ? (int)ic : 0]); });
         } else {
             M &m = *launder(mp);
@@ -1004,17 +1035,26 @@ MPPI_HD QF quad_rollout(M &m0, CCfg &cfg0, CCost &cost0, LStep &sc, const float 
         quad_step<T>(*mp, P, q, qd, target, ab);
         if constexpr (DUMP) {  // (the four lanes of a quad hold the same values: same-address stores, as for du)
             const unsigned HK = (unsigned)H * (unsigned)K, col = (unsigned)t * (unsigned)K + (unsigned)k;
-            static_for<0, NB>([&](auto ic) MPPI_LAMBDA {
-                constexpr int i = ic;
-                traj[(unsigned)i * HK + col] = qlane0(q[i]);
-                traj[(unsigned)(NB + i) * HK + col] = qlane0(qd[i]);
-            });
+            if constexpr (JV) {
+                ab.dump(q, qd, traj, HK, col);
+            } else {
+                static_for<0, NB>([&](auto ic) MPPI_LAMBDA {
+                    constexpr int i = ic;
+                    traj[(unsigned)i * HK + col] = qlane0(q[i]);
+                    traj[(unsigned)(NB + i) * HK + col] = qlane0(qd[i]);
+                });
+            }
         }
         QM3 Rl;  // pose of the cost link, shared with the rollout visualisation when that shows the same link
         QF pl = qrep(0.f);
         for (int c = 0; c < 3; c++) Rl.c[c] = qrep(0.f);
         if (need_link) quad_link_pose<T>(*launder(mp), P, link, Rl, pl);
-        S += disc * quad_stage_cost<T>(kind, sc, q, Rl, pl);
+        if constexpr (JV) {   // (the point cost reads q0, q1 replicated: two broadcasts per horizon step)
+            const QF qxy[2] = {ab.template joint<0>(q), ab.template joint<(NB > 1 ? 1 : 0)>(q)};
+            S += disc * quad_stage_cost<T>(kind, sc, qxy, Rl, pl);
+        } else {
+            S += disc * quad_stage_cost<T>(kind, sc, q, Rl, pl);
+        }
         disc *= gamma;
         if (want_viz) {
             QM3 R;
