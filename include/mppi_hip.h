@@ -456,6 +456,23 @@ int mppi_sim_materialise_mirror(mppi_ctx_t *ctx, float *dof_dev, float *root_dev
 int mppi_mirror_wait(mppi_ctx_t *ctx, float *dof_host, float *root_host);
 /* reference-layout tensors: dof [K][2n], root [K][A][13], rb [K][B][13], cf [K][B][3]; NULL = skip */
 int mppi_sim_materialise(mppi_ctx_t *ctx, float *dof_dev, float *root_dev, float *rb_dev, float *cf_dev);
+/* How the robot of every env RESPONDS, at the envs' current joint positions (device tensors, env-major like the four above):
+ *   mppi_sim_jacobian     replaces gym.acquire_jacobian_tensor / refresh_jacobian_tensors: for the rigid bodies rb_first ..
+ *                         rb_first + rb_count - 1 the 6 x n_dof block J with  J qd = columns 7:13 of that body's rigid-body row -
+ *                         rows 0-2 the velocity of the link frame origin, rows 3-5 the angular velocity, world axes.  A revolute
+ *                         joint on the path from the base to the link contributes (a x (p_link - p_joint), a), a prismatic one
+ *                         (a, 0), every other joint a zero column.  Bodies that belong to no robot (box / sphere actors) and links
+ *                         welded to the fixed base get zero blocks: the block index IS the rigid-body index (gym drops the fixed
+ *                         root link's block and shifts the index by one).
+ *   mppi_sim_mass_matrix  replaces gym.acquire_mass_matrix_tensor / refresh_mass_matrix_tensors: the joint-space inertia M(q) of
+ *                         the packed model (composite rigid bodies), symmetric bit for bit.  No drive terms: the implicit-drive
+ *                         h kd / h^2 kp that the step adds to the joint-space diagonal is not in it.
+ * n_dof is the forest's for a fixed-base forest of several robots (columns of another robot's joints are zero, M is block diagonal).
+ * Launches on the context's stream only - no allocation, no copy, no synchronise: both can sit in a captured graph.
+ * MPPI_EINVAL: a null pointer, a range outside [0, n_rb).  MPPI_EUNSUPPORTED (mppi_last_error says so): a robot with a MOVING
+ * base - the six floating-base columns are not computed, and the result is refused rather than returned without them. */
+int mppi_sim_jacobian(mppi_ctx_t *ctx, int rb_first, int rb_count, float *jac_dev);  /* [K][rb_count][6][n_dof] */
+int mppi_sim_mass_matrix(mppi_ctx_t *ctx, float *M_dev);                              /* [K][n_dof][n_dof]       */
 int mppi_sim_accumulate_cost(mppi_ctx_t *ctx, int t, const float *cost_dev); /* S += gamma^t c      */
 int mppi_sim_finish(mppi_ctx_t *ctx);                      /* S += control cost                     */
 /* The same horizon in TWO launches for host-side costs that are functions of the state tensors (mppi_isaac.py:57-69 evaluates

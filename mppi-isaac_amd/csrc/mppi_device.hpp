@@ -1115,4 +1115,187 @@ MPPI_HD void rigid_body_link(CModel &m, const float *root, const float *q, const
     o[10] = vb.a.x; o[11] = vb.a.y; o[12] = vb.a.z;
 }
 
+// ---- link Jacobians and joint-space mass matrix of one env of a FIXED-base robot (mppi_sim_jacobian / mppi_sim_mass_matrix) ----
+// bodies on the path from the base to body i, body i included, as a bit mask: a compile-time fact of the tree
+template <class T>
+constexpr unsigned ancestor_mask(int i) {
+    unsigned mask = 0;
+    while (i >= 0) {
+        mask |= 1u << i;
+        i = T::par[i];
+    }
+    return mask;
+}
+// the child of body p that the leaves-to-root sweep reaches first (the highest index; -1: a leaf)
+template <class T>
+constexpr int last_child(int p) {
+    int c = -1;
+    for (int i = 0; i < T::NB; i++)
+        if (T::par[i] == p) c = i;
+    return c;
+}
+
+// Both tensors are built from RELATIVE offsets only: d[i] = p_i - p_parent(i) in world axes, formed as R_parent pt_i (+ q_i a_i for
+// a prismatic joint) and never as a difference of world positions, whose last bit is 3e-5 m a few hundred metres from the origin
+// - where the prismatic base joints of the mobile manipulators can carry the arm.  Neither result depends on where the base stands.
+// forward_kinematics_base (the base pose already in P.Rb / P.pb) that also hands out those offsets; every body's block is fetched
+// where it is used (launder): kept in scalar registers across the whole tree, twelve 16-dword blocks do not fit.
+template <class T, class M>
+MPPI_HD void forward_kinematics_offsets(M &m0, const float *q, Pose<T> &P, V3 *d) {
+    M *mp = &m0;
+    static_for<0, T::NB>([&](auto ic) MPPI_LAMBDA {
+        constexpr int i = ic;
+        constexpr int par = T::par[i];
+        const BodyK0 b = load_block<BodyK0>(launder(mp)->b[i].k0);
+        P.jt[i] = b.jtype;
+        const M3 &Rp = par < 0 ? P.Rb : P.R[par < 0 ? 0 : par];
+        const V3 pp = par < 0 ? P.pb : P.p[par < 0 ? 0 : par];
+        M3 Rt0;
+        for (int j = 0; j < 9; j++) Rt0.a[j] = b.rt(j);
+        const M3 RT = mul(Rp, Rt0);
+        const V3 off = mul(Rp, V3{b.pt(0), b.pt(1), b.pt(2)});
+        if (b.jtype == 0) {  // revolute about local z: R = RT * Rz(q)
+            float s, c;
+            fast_sincos(q[i], s, c);
+            M3 R;
+            for (int r = 0; r < 3; r++) {
+                R.a[3 * r + 0] = c * RT.a[3 * r] + s * RT.a[3 * r + 1];
+                R.a[3 * r + 1] = c * RT.a[3 * r + 1] - s * RT.a[3 * r];
+                R.a[3 * r + 2] = RT.a[3 * r + 2];
+            }
+            P.R[i] = R;
+            d[i] = off;
+        } else {  // prismatic along local z
+            P.R[i] = RT;
+            d[i] = off + q[i] * V3{RT.a[2], RT.a[5], RT.a[8]};
+        }
+        P.p[i] = pp + d[i];
+    });
+}
+
+// J [6][NB] (row-major) of robot link l for the body poses P:  J qd = columns 7:13 of the link's rigid-body row as
+// rigid_body_state reports it - rows 0-2 the velocity of the link frame origin, rows 3-5 the angular velocity, world axes.
+// Column i is (a_i x (p_link - p_i), a_i) for a revolute joint i on the path from the base to the link's body, (a_i, 0) for a
+// prismatic one, zero for every other joint.  The lever arm p_link - p_i is the sum of the offsets along the path (body_offsets),
+// collected on the way from the link's body to the base.  l outside [0, nl) (the body of a box or sphere actor) and links
+// welded to the fixed base give a zero block.
+template <class T, class M>
+MPPI_HD void link_jacobian(M &m, const Pose<T> &P, const V3 *d, int l, float *J) {
+    constexpr int NB = T::NB;
+    const bool robot = l >= 0 && l < m.nl;
+    const int ll = robot ? l : 0;
+    const int body = robot ? m.l[ll].body : -1;
+    unsigned anc = 0;
+    M3 Rb;  // rotation of the link's body: a 0/1-weighted blend, as link_pose
+    for (int j = 0; j < 9; j++) Rb.a[j] = 0.f;
+    static_for<0, NB>([&](auto ic) MPPI_LAMBDA {
+        constexpr int i = ic;
+        anc = body == i ? ancestor_mask<T>(i) : anc;
+        const float w = body == i ? 1.f : 0.f;
+        for (int j = 0; j < 9; j++) Rb.a[j] += w * P.R[i].a[j];
+    });
+    V3 arm = mul(Rb, loadv(m.l[ll].p));  // p_link - p_body, then p_link - p_i on the way up
+    static_rfor<0, NB>([&](auto ic) MPPI_LAMBDA {
+        constexpr int i = ic;
+        const bool on = ((anc >> i) & 1u) != 0, rev = P.jt[i] == 0;
+        const V3 az = {P.R[i].a[2], P.R[i].a[5], P.R[i].a[8]};
+        const V3 lin = rev ? cross(az, arm) : az;
+        J[0 * NB + i] = on ? lin.x : 0.f;
+        J[1 * NB + i] = on ? lin.y : 0.f;
+        J[2 * NB + i] = on ? lin.z : 0.f;
+        J[3 * NB + i] = on && rev ? az.x : 0.f;
+        J[4 * NB + i] = on && rev ? az.y : 0.f;
+        J[5 * NB + i] = on && rev ? az.z : 0.f;
+        if (on) arm = arm + d[i];
+    });
+}
+
+// M [NB][NB] (row-major) at the body poses P: the composite-rigid-body inertia of the packed model, no drive terms.
+// Every composite inertia (mass, first moment h = m (c - p_i), rotational inertia I) is carried about ITS OWN body origin p_i in
+// world axes and moved to the parent by the relative offset d[i] = p_i - p_parent only: about the world origin a wrist joint's
+// S^T I S of 1e-3 kg m^2 would be what is left of terms m |c|^2 of order 1, and less the further the base stands from the origin
+// ("One row found something").  Both triangles are written from the same value.
+template <class T, class M>
+MPPI_HD void mass_matrix(M &m0, const Pose<T> &P, const V3 *d, float *Mo) {
+    constexpr int NB = T::NB;
+    M *mp = &m0;
+    float cm[NB ? NB : 1];
+    V3 ch[NB ? NB : 1];
+    S3 cI[NB ? NB : 1];
+    static_rfor<0, NB>([&](auto ic) MPPI_LAMBDA {
+        constexpr int i = ic;
+        constexpr int par = T::par[i];
+        const BodyK1 b = load_block<BodyK1>(launder(mp)->b[i].k1);  // (fetched where it is used, as in body_offsets)
+        const M3 &R = P.R[i];
+        // the body's own inertia about p_i: I = R Ic R^T + m (|c|^2 1 - c c^T), h = m c, c = R com
+        const V3 h = mul(R, V3{b.hb(0), b.hb(1), b.hb(2)});
+        float T9[9];  // R * Ic
+        for (int r = 0; r < 3; r++) {
+            const float r0 = R.a[3 * r], r1 = R.a[3 * r + 1], r2 = R.a[3 * r + 2];
+            T9[3 * r + 0] = r0 * b.Ic(0) + r1 * b.Ic(1) + r2 * b.Ic(2);
+            T9[3 * r + 1] = r0 * b.Ic(1) + r1 * b.Ic(3) + r2 * b.Ic(4);
+            T9[3 * r + 2] = r0 * b.Ic(2) + r1 * b.Ic(4) + r2 * b.Ic(5);
+        }
+        const V3 c = b.invm * h;
+        const float hh = dot(h, c);
+        S3 I;
+        I.xx = T9[0] * R.a[0] + T9[1] * R.a[1] + T9[2] * R.a[2] + hh - h.x * c.x;
+        I.xy = T9[0] * R.a[3] + T9[1] * R.a[4] + T9[2] * R.a[5] - h.x * c.y;
+        I.xz = T9[0] * R.a[6] + T9[1] * R.a[7] + T9[2] * R.a[8] - h.x * c.z;
+        I.yy = T9[3] * R.a[3] + T9[4] * R.a[4] + T9[5] * R.a[5] + hh - h.y * c.y;
+        I.yz = T9[3] * R.a[6] + T9[4] * R.a[7] + T9[5] * R.a[8] - h.y * c.z;
+        I.zz = T9[6] * R.a[6] + T9[7] * R.a[7] + T9[8] * R.a[8] + hh - h.z * c.z;
+        float mc = b.m;
+        V3 hc = h;
+        if constexpr (last_child<T>(i) >= 0) {  // the subtrees below, already about p_i
+            mc += cm[i];
+            hc = hc + ch[i];
+            I.xx += cI[i].xx; I.xy += cI[i].xy; I.xz += cI[i].xz; I.yy += cI[i].yy; I.yz += cI[i].yz; I.zz += cI[i].zz;
+        }
+        // spatial force (moment n about p_i, force f) of a unit acceleration of joint i acting on the composite body
+        const V3 az = {R.a[2], R.a[5], R.a[8]};
+        const bool rev = P.jt[i] == 0;
+        const V3 f = rev ? cross(az, hc) : mc * az;
+        V3 n = rev ? mul(I, az) : cross(hc, az);
+        Mo[i * NB + i] = rev ? dot(az, n) : mc;
+        V3 up = d[i];  // from the origin the moment is taken about to the next body on the way to the base
+        static_rfor<0, i>([&](auto jc) MPPI_LAMBDA {
+            constexpr int j = jc;
+            float v = 0.f;
+            if constexpr (((ancestor_mask<T>(i) >> j) & 1u) != 0) {
+                n = n + cross(up, f);  // the same force, moment about p_j
+                up = d[j];
+                const V3 aj = {P.R[j].a[2], P.R[j].a[5], P.R[j].a[8]};
+                v = P.jt[j] == 0 ? dot(aj, n) : dot(aj, f);
+            }
+            Mo[i * NB + j] = v;
+            Mo[j * NB + i] = v;
+        });
+        if constexpr (par >= 0) {
+            // to the parent's origin: h' = h + m d, I' = I + 2 (e.d) 1 - (e d^T + d e^T) with e = h + m d / 2
+            constexpr int pj = par < 0 ? 0 : par;
+            const V3 dd = d[i];
+            const V3 e = hc + (0.5f * mc) * dd;
+            const float ed = 2.f * dot(e, dd);
+            S3 Ip;
+            Ip.xx = I.xx + ed - 2.f * e.x * dd.x;
+            Ip.yy = I.yy + ed - 2.f * e.y * dd.y;
+            Ip.zz = I.zz + ed - 2.f * e.z * dd.z;
+            Ip.xy = I.xy - (e.x * dd.y + dd.x * e.y);
+            Ip.xz = I.xz - (e.x * dd.z + dd.x * e.z);
+            Ip.yz = I.yz - (e.y * dd.z + dd.y * e.z);
+            const V3 hp = hc + mc * dd;
+            if constexpr (last_child<T>(pj) == i) {
+                cm[pj] = mc;
+                ch[pj] = hp;
+                cI[pj] = Ip;
+            } else {
+                cm[pj] += mc;
+                ch[pj] = ch[pj] + hp;
+                cI[pj].xx += Ip.xx; cI[pj].xy += Ip.xy; cI[pj].xz += Ip.xz; cI[pj].yy += Ip.yy; cI[pj].yz += Ip.yz; cI[pj].zz += Ip.zz;
+            }
+        }
+    });
+}
+
 }  // namespace mppi

@@ -1338,6 +1338,41 @@ int mppi_sim_materialise(mppi_ctx_t *c, float *dof, float *root, float *rb, floa
     c->launch_materialise(c, dof, root, rb, cf);
     return launch_check();
 }
+namespace {
+// the launch-table row of a context's tree (mppi_create found or built it: a table walk, no allocation), or an error code when
+// the entry cannot serve `what`: the Jacobian columns / the rows and columns of M that belong to a MOVING base are not computed
+int physics_entry(mppi_ctx *c, const char *what, const TopoEntry *&e) {
+    if (c->hm.floating || c->hm.n_bases > 1)
+        return fail(MPPI_EUNSUPPORTED, std::string(what) + ": unsupported for a robot with a moving base (the six floating-base columns are not computed); "
+                                       "fixed-base robots and fixed-base forests only");
+    int parents[MPPI_MAX_BODIES];
+    for (int i = 0; i < c->hm.nb; i++) parents[i] = c->hm.b[i].k0.parent;
+    e = find_entry(c->hm.nb, parents, c->scene, c->hm.n_free);
+    if (!e || !e->sim_jacobian || !e->sim_mass_matrix) return fail(MPPI_EUNSUPPORTED, std::string(what) + ": not available for this kinematic tree");
+    return MPPI_OK;
+}
+}  // namespace
+/* the two remaining physics tensors of gym's tensor API, from the envs' current joint positions: launches on the context's stream,
+ * no allocation, no copy, no synchronise (include/mppi_hip.h) */
+int mppi_sim_jacobian(mppi_ctx_t *c, int rb_first, int rb_count, float *jac_dev) {
+    CTX_TRY(c);
+    if (!jac_dev) return fail(MPPI_EINVAL, "mppi_sim_jacobian: null output");
+    if (rb_first < 0 || rb_count < 1 || rb_first >= c->B || rb_count > c->B - rb_first)
+        return fail(MPPI_EINVAL, "mppi_sim_jacobian: rigid bodies [" + std::to_string(rb_first) + ", " + std::to_string((long long)rb_first + rb_count) + ") outside [0, " +
+                                     std::to_string(c->B) + ")");
+    const TopoEntry *e = nullptr;
+    if (int rc = physics_entry(c, "mppi_sim_jacobian", e)) return rc;
+    e->sim_jacobian(c, rb_first, rb_count, jac_dev);
+    return launch_check();
+}
+int mppi_sim_mass_matrix(mppi_ctx_t *c, float *M_dev) {
+    CTX_TRY(c);
+    if (!M_dev) return fail(MPPI_EINVAL, "mppi_sim_mass_matrix: null output");
+    const TopoEntry *e = nullptr;
+    if (int rc = physics_entry(c, "mppi_sim_mass_matrix", e)) return rc;
+    e->sim_mass_matrix(c, M_dev);
+    return launch_check();
+}
 int mppi_sim_accumulate_cost(mppi_ctx_t *c, int t, const float *cost_dev) {
     CTX_TRY(c);
     if (!cost_dev) return fail(MPPI_EINVAL, "null cost");

@@ -1741,6 +1741,77 @@ __global__ __launch_bounds__(kWave) void k_materialise_link(const DevModel *__re
     }
 }
 
+// ---- link Jacobians and joint-space mass matrix of the batched simulator's envs (mppi_sim_jacobian / mppi_sim_mass_matrix) ----
+// One env per lane computes its row (6 n or n^2 floats) into LDS; the wavefront's rows are then stored coalesced, as
+// k_materialise_link stores its 13-float rows.  A lane writes its row at stride kStride dwords: odd, so the 32 lanes of a
+// ds_write group hit 32 different banks (an even row length - 144 for the 12 joints of the mobile manipulator - would put them
+// on two).
+constexpr int staged_stride(int len) { return len | 1; }
+// rows 0 .. n_rows-1 of the staged tile -> out[r * pitch + c]: consecutive lanes store consecutive floats of a row
+template <int LEN>
+__device__ __forceinline__ void store_staged_rows(const float *s_row, int n_rows, float *__restrict__ out, size_t pitch) {
+    constexpr int kStride = staged_stride(LEN);
+    for (int e = threadIdx.x; e < n_rows * LEN; e += kWave) {
+        const int r = e / LEN, c = e - r * LEN;
+        out[(size_t)r * pitch + c] = s_row[r * kStride + c];
+    }
+}
+// body poses and parent-to-child offsets of env k: joint positions from the sample-minor q_, the fixed base from x0_root - or, for
+// the envs of a contact-scene context, from the base rows k_materialise_scene reads
+template <class T>
+__device__ __forceinline__ void sim_env_pose(CModel &M, int K, int k, const float *__restrict__ x0_root, const float *__restrict__ q_,
+                                             const float *__restrict__ base_, Pose<T> &P, V3 *d) {
+    constexpr int NB = T::NB;
+    float q[NB ? NB : 1], row[7];
+    static_for<0, NB>([&](auto ic) {
+        constexpr int i = ic;
+        q[i] = q_[(size_t)i * K + k];
+    });
+    for (int j = 0; j < 7; j++) row[j] = base_ != nullptr ? base_[(size_t)j * K + k] : x0_root[13 * M.robot_actor + j];
+    P.pb = loadv(row);
+    P.Rb = quat_to_R(row + 3);
+    forward_kinematics_offsets<T>(M, q, P, d);
+}
+// out [K][rb_count][6][n]: the Jacobians of rigid bodies rb_first .. rb_first + rb_count - 1 (link_jacobian, mppi_device.hpp;
+// zero blocks for bodies that are no robot link).  One staging pass per body: the tile stays one row per lane.
+template <class T>
+__global__ __launch_bounds__(kWave) void k_sim_jacobian(const DevModel *__restrict__ m, int K, const float *__restrict__ x0_root,
+                                                        const float *__restrict__ q_, const float *__restrict__ base_, int rb_first, int rb_count,
+                                                        float *__restrict__ out) {
+    constexpr int kLen = 6 * T::NB, kStride = staged_stride(kLen);
+    __shared__ float s_row[kWave * kStride];
+    CModel &M = *(CModel *)m;
+    const int k0 = blockIdx.x * kWave, k = k0 + threadIdx.x;
+    const int n_rows = K - k0 < kWave ? K - k0 : kWave;
+    Pose<T> P;
+    V3 d[T::NB ? T::NB : 1];
+    if (k < K) sim_env_pose<T>(M, K, k, x0_root, q_, base_, P, d);
+    for (int j = 0; j < rb_count; j++) {
+        if (k < K) link_jacobian<T>(M, P, d, rb_first + j - M.robot_first_rb, s_row + threadIdx.x * kStride);
+        __syncthreads();
+        store_staged_rows<kLen>(s_row, n_rows, out + ((size_t)k0 * rb_count + j) * kLen, (size_t)rb_count * kLen);
+        __syncthreads();
+    }
+}
+// out [K][n][n]: M(q) of every env (mass_matrix, mppi_device.hpp)
+template <class T>
+__global__ __launch_bounds__(kWave) void k_sim_mass_matrix(const DevModel *__restrict__ m, int K, const float *__restrict__ x0_root,
+                                                           const float *__restrict__ q_, const float *__restrict__ base_, float *__restrict__ out) {
+    constexpr int kLen = T::NB * T::NB, kStride = staged_stride(kLen);
+    __shared__ float s_row[kWave * kStride];
+    CModel &M = *(CModel *)m;
+    const int k0 = blockIdx.x * kWave, k = k0 + threadIdx.x;
+    const int n_rows = K - k0 < kWave ? K - k0 : kWave;
+    if (k < K) {
+        Pose<T> P;
+        V3 d[T::NB ? T::NB : 1];
+        sim_env_pose<T>(M, K, k, x0_root, q_, base_, P, d);
+        mass_matrix<T>(M, P, d, s_row + threadIdx.x * kStride);
+    }
+    __syncthreads();
+    store_staged_rows<kLen>(s_row, n_rows, out + (size_t)k0 * kLen, kLen);
+}
+
 // Parity / debug entry (mppi_eval_cost): the cost program of the context evaluated by the interpreter the rollout kernels run
 // (program_cost_with, mppi_device.hpp) on CALLER-GIVEN simulator answers - reference-layout rows of n envs - instead of the
 // kernel's own kinematics: link poses from the rigid-body rows (position, quaternion xyzw), actor rows from the root rows,
@@ -1930,6 +2001,8 @@ struct TopoEntry {
     void (*materialise_scene)(mppi_ctx *, float *, float *, float *, float *);
     void (*combine_world)(mppi_ctx *, const float *, int, mppi_ctx *);
     void (*eval_cost)(mppi_ctx *, int, const float *, const float *, const float *, const float *, float *);  // mppi_eval_cost
+    void (*sim_jacobian)(mppi_ctx *, int, int, float *);  // mppi_sim_jacobian (null: not built for this tree)
+    void (*sim_mass_matrix)(mppi_ctx *, float *);         // mppi_sim_mass_matrix
     hipError_t (*raise_lds)(size_t, size_t);
     size_t (*static_lds)();  // largest static __shared__ footprint among the contact-scene kernels (counts against the 160 KiB too)
 };
@@ -2101,6 +2174,16 @@ template <class T>
 void launch_eval_cost_t(mppi_ctx *c, int n, const float *dof, const float *root, const float *rb, const float *cf, float *out) {
     hipLaunchKernelGGL(k_eval_cost<T>, dim3((n + kWave - 1) / kWave), dim3(kWave), 0, c->stream, c->d_model, c->d_cost, n, dof, root, rb, cf, out);
 }
+// (the envs of a contact-scene context keep the robot's base rows per env - d_base -, those of a contact-free one share x0_root)
+template <class T>
+void launch_sim_jacobian_t(mppi_ctx *c, int rb_first, int rb_count, float *out) {
+    hipLaunchKernelGGL(k_sim_jacobian<T>, dim3(c->n_waves), dim3(kWave), 0, c->stream, c->d_model, c->K, c->d_x0_root, c->d_q, c->scene ? c->d_base : nullptr,
+                       rb_first, rb_count, out);
+}
+template <class T>
+void launch_sim_mass_matrix_t(mppi_ctx *c, float *out) {
+    hipLaunchKernelGGL(k_sim_mass_matrix<T>, dim3(c->n_waves), dim3(kWave), 0, c->stream, c->d_model, c->K, c->d_x0_root, c->d_q, c->scene ? c->d_base : nullptr, out);
+}
 template <class T>
 void launch_rollout_t(mppi_ctx *c) { launch_rollout_kernel(k_rollout<T>, c->n_waves, kWave, 0, c); }
 template <class T>
@@ -2140,6 +2223,10 @@ void fill_topo_entry_free(TopoEntry &e) {
     e.materialise = &launch_materialise_t<T>;
     e.combine_world = &launch_combine_world_t<T>;
     e.eval_cost = &launch_eval_cost_t<T>;
+    if constexpr (T::NBASE == 1) {  // (forests of several moving bases are refused by both entries: nothing to launch)
+        e.sim_jacobian = &launch_sim_jacobian_t<T>;
+        e.sim_mass_matrix = &launch_sim_mass_matrix_t<T>;
+    }
 }
 template <class T>
 void fill_topo_entry_scene(TopoEntry &e) {

@@ -153,6 +153,8 @@ _SIGNATURES = {
     "mppi_sim_materialise_mirror": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "mppi_mirror_wait": (C.c_int, [_vp, _fp, _fp]),
     "mppi_sim_materialise": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "mppi_sim_jacobian": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
+    "mppi_sim_mass_matrix": (C.c_int, [_vp, _vp]),
     "mppi_sim_accumulate_cost": (C.c_int, [_vp, C.c_int, _vp]),
     "mppi_sim_finish": (C.c_int, [_vp]),
     "mppi_rollout_trajectory": (C.c_int, [_vp]),

@@ -562,6 +562,11 @@ class Scene:
         return m
 
 
+class PerStepOnly(RuntimeError):
+    """an accessor that answers for the simulator's LIVE envs only was called inside a planner's horizon view (whose rows are
+    the precomputed states of a whole horizon): planner/mppi.py then runs the Objective step by step on the stepped envs"""
+
+
 def _dev_ptr(t: Optional[torch.Tensor]):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
@@ -641,6 +646,7 @@ class IsaacGymWrapper:
         self._state_t_own = self._state_t
         self._state_ptrs = tuple(_dev_ptr(self._state_t[k]) for k in ("dof", "root", "rb", "cf"))
         self._stale, self._needs_reset = True, False
+        self._jacobians, self._mass_matrix = {}, None   # acquire_jacobian_tensor / acquire_mass_matrix_tensor: filled by refresh_*()
         self._visualize_link_present = sc.viz_link_index() >= 0
         self.visualize_link_buffer = []
         if self._visualize_link_present:
@@ -959,6 +965,60 @@ class IsaacGymWrapper:
 
     def get_dof_state(self):
         return self._dof_state
+
+    # ------------------------------------------------------------------ link Jacobians and joint-space mass matrix
+    # gym.acquire_jacobian_tensor / acquire_mass_matrix_tensor and their refresh calls: the acquired tensors are written by
+    # refresh_*() only - explicit, as in Isaac Gym - from the envs' current joint positions.  Fixed-base robots (and fixed-base
+    # forests: n_dof is the forest's); a moving base raises NotImplementedError with the library's text.  One deviation: the
+    # fixed root link keeps its (zero) block, so the Jacobian's link index IS the rigid-body index within the actor (Isaac Gym
+    # drops that block and shifts the index by one).
+    def _physics_call(self, fn, *args):
+        """a launch of one of the two entries: per step only, a moving base refused with the library's reason"""
+        if self._state_t is not self._state_t_own:
+            raise PerStepOnly("link Jacobians and the mass matrix are per-step only: they are computed from the live envs, not from the "
+                              "precomputed states of a planner's horizon view")
+        self._reset_envs_if_needed()
+        rc = fn(self._ctx, *args)
+        if rc == capi.MPPI_EUNSUPPORTED:
+            raise NotImplementedError(self._lib.mppi_last_error().decode())
+        capi.check(self._lib, rc)
+
+    def _actor_rb_range(self, actor_name: str):
+        a = self.scene.actor_index(actor_name)
+        m = self._c_model
+        return int(m.actors[a].first_rb), int(m.actors[a].n_rb)
+
+    def acquire_jacobian_tensor(self, actor_name: str):
+        """[K, L, 6, n_dof]: one 6 x n_dof block per rigid body of the actor, in rigid-body order (rows 0-2 linear, 3-5 angular,
+        world axes; J @ qd = columns 7:13 of the body's rigid-body row).  Zero until refresh_jacobian_tensors()."""
+        if actor_name not in self._jacobians:
+            first, count = self._actor_rb_range(actor_name)
+            t = torch.zeros((self.num_envs, count, 6, self.scene.n_dof), dtype=torch.float32, device=self.device)
+            self._jacobians[actor_name] = (first, count, t)
+        return self._jacobians[actor_name][2]
+
+    def acquire_mass_matrix_tensor(self, actor_name: str):
+        """[K, n_dof, n_dof]: the joint-space inertia M(q) of every env, symmetric, without drive terms.  Zero until
+        refresh_mass_matrix_tensors()."""
+        self.scene.actor_index(actor_name)
+        if self._mass_matrix is None:
+            self._mass_matrix = torch.zeros((self.num_envs, self.scene.n_dof, self.scene.n_dof), dtype=torch.float32, device=self.device)
+        return self._mass_matrix
+
+    def refresh_jacobian_tensors(self) -> None:
+        for first, count, t in self._jacobians.values():
+            self._physics_call(self._lib.mppi_sim_jacobian, first, count, _dev_ptr(t))
+
+    def refresh_mass_matrix_tensors(self) -> None:
+        if self._mass_matrix is not None:
+            self._physics_call(self._lib.mppi_sim_mass_matrix, _dev_ptr(self._mass_matrix))
+
+    def get_actor_link_jacobian_by_name(self, actor_name: str, link_name: str):
+        """a fresh dense [K, 6, n_dof] Jacobian of one link (a one-body launch): the counterpart of get_actor_link_by_name"""
+        rb = self.scene.rigid_body_index(actor_name, link_name)
+        out = torch.empty((self.num_envs, 6, self.scene.n_dof), dtype=torch.float32, device=self.device)
+        self._physics_call(self._lib.mppi_sim_jacobian, rb, 1, _dev_ptr(out))
+        return out
 
     # ------------------------------------------------------------------ env mutation (reference :423-427, :695-758)
     def _restart(self):

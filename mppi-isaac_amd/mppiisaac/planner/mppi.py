@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from mppiisaac.backend import capi
+from mppiisaac.planner.isaacgym_wrapper import PerStepOnly
 
 
 @dataclass
@@ -465,6 +466,8 @@ class MPPIPlanner:
         if self._batch_state == "off" or (self._prior is not None and self.cfg.use_priors):
             return False
         sig = self._objective_signature()
+        if self._batch_sig == ("per-step", sig):
+            return False
         b = self._simulate_horizon()
         single = self._batch_state == "on" or self._batch_sig == ("ok", sig)
         # an Objective whose Python-side state drifts AFTER its first command (a call counter that starts to matter, a schedule)
@@ -484,6 +487,16 @@ class MPPIPlanner:
             S_one = None
             try:
                 S_one = self._horizon_costs(state, b, single=True)
+            except PerStepOnly as e:
+                # the Objective reads what exists for the LIVE envs only (link Jacobians, mass matrix): neither a view of the whole
+                # horizon nor its [K]-row blocks can answer - the reference's loop shape (step, cost, step, ...) from here on
+                import logging
+                logging.getLogger("mppiisaac").warning("the Objective runs per step (one simulator step and one compute_cost call per horizon "
+                                                       "step), not on the precomputed states of the horizon: %s", e)
+                self._batch_sig = ("per-step", sig)
+                self.sim.visualize_link_buffer = viz
+                capi.check(self._lib, self._lib.mppi_sim_reset(self._ctx))   # (the simulated horizon left its control cost behind)
+                return False
             except Exception as e:  # noqa: BLE001 - e.g. an Objective with tensors sized for K envs
                 warnings.warn(f"the Objective cannot be evaluated over a whole horizon in one call ({type(e).__name__}: {e}); "
                               "keeping one compute_cost call per horizon step")
