@@ -691,6 +691,11 @@ __device__ __forceinline__ void combine_update(CCfg &cfg, const float *__restric
             float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
             float4 v[kWideLoads];
             const int nvalid = HN - 4 * cq;  // >= 4 except in the last quad of a ragged row count
+            // a skipped record (factor 0) is not read into the sum: 0 * NaN of a stale or half-written slot is NaN (selects, no branch)
+            auto live4 = [](const float4 &w, float sc) {
+                const bool on = sc != 0.f;
+                return make_float4(on ? w.x : 0.f, on ? w.y : 0.f, on ? w.z : 0.f, on ? w.w : 0.f);
+            };
             auto load4 = [&](int r, float4 &w) {
                 const float *src = recs + (size_t)r * RF + 2 + 4 * cq;
                 if (nvalid >= 4) __builtin_memcpy(&w, src, 16);
@@ -711,7 +716,8 @@ __device__ __forceinline__ void combine_update(CCfg &cfg, const float *__restric
                 const int r = g + i * G;
                 if (r < nrec) {
                     const float sc = s_scale[r];
-                    acc.x += v[i].x * sc; acc.y += v[i].y * sc; acc.z += v[i].z * sc; acc.w += v[i].w * sc;
+                    const float4 x = live4(v[i], sc);
+                    acc.x += x.x * sc; acc.y += x.y * sc; acc.z += x.z * sc; acc.w += x.w * sc;
                 }
             }
 #pragma unroll 8
@@ -719,7 +725,8 @@ __device__ __forceinline__ void combine_update(CCfg &cfg, const float *__restric
                 float4 w;
                 load4(r, w);
                 const float sc = s_scale[r];
-                acc.x += w.x * sc; acc.y += w.y * sc; acc.z += w.z * sc; acc.w += w.w * sc;
+                const float4 x = live4(w, sc);
+                acc.x += x.x * sc; acc.y += x.y * sc; acc.z += x.z * sc; acc.w += x.w * sc;
             }
             float *o = s_flat + g * HN + 4 * cq;
             o[0] = acc.x;
@@ -740,7 +747,8 @@ __device__ __forceinline__ void combine_update(CCfg &cfg, const float *__restric
                         const float er = recs[(size_t)r * RF + 1];
                         sc = er > 0.f ? __expf(-(recs[(size_t)r * RF] - beta) * cfg.inv_lambda) : 0.f;
                     }
-                    N0 += recs[(size_t)r * RF + 2 + j] * sc;
+                    const float v = recs[(size_t)r * RF + 2 + j];
+                    N0 += (sc != 0.f ? v : 0.f) * sc;
                 }
                 s_part[g][j] = N0;
             }
