@@ -171,5 +171,40 @@ float emu_cost(const mppi_model_t *model, const mppi_cost_t *cost, const float *
     });
     return out;
 }
+
+// what mppi_eval_cost launches (k_eval_cost, mppi_kernels.hpp): the cost program of n envs interpreted on CALLER-GIVEN rows -
+// link poses from the rigid-body rows, actor rows from the root rows, contact forces as given
+struct EmuGivenEnv {
+    const float *root, *cfr;
+    V3 vec(int actor, int off) const { return loadv(root + 13 * actor + off); }
+    void quat(int actor, float *qq) const {
+        for (int j = 0; j < 4; j++) qq[j] = root[13 * actor + 3 + j];
+    }
+    float cf(int rb, int j) const { return cfr[3 * rb + j]; }
+    V3 constant_point(float x, float y, float z) const { return V3{x, y, z}; }
+};
+int emu_eval_cost(const mppi_model_t *model, const mppi_cost_t *cost, int n, const float *dof, const float *root, const float *rb, const float *cf,
+                  float *out) {
+    DevModel m; DevCost k; std::string err;
+    if (!pack_model(*model, m, err) || !pack_cost(*cost, m, k, err)) return -1;
+    if (k.kind != MPPI_COST_PROGRAM) return -1;
+    int parents[MPPI_MAX_BODIES];
+    for (int i = 0; i < m.nb; i++) parents[i] = m.b[i].k0.parent;
+    bool ok = dispatch_topology(m.nb, parents, [&](auto topo) {
+        using T = decltype(topo);
+        constexpr int NB = T::NB;
+        for (int e = 0; e < n; e++) {
+            float q[NB ? NB : 1], qd[NB ? NB : 1];
+            for (int i = 0; i < NB; i++) { q[i] = dof[(size_t)e * 2 * NB + 2 * i]; qd[i] = dof[(size_t)e * 2 * NB + 2 * i + 1]; }
+            const float *rows = rb + (size_t)e * 13 * m.n_rb + 13 * m.robot_first_rb;
+            const EmuGivenEnv env{root + (size_t)e * 13 * m.n_actors, cf + (size_t)e * 3 * m.n_rb};
+            out[e] = program_cost_with<T>(k, q, qd, [&](int l, M3 &R, V3 &p) {
+                p = loadv(rows + 13 * l);
+                R = quat_to_R(rows + 13 * l + 3);
+            }, env);
+        }
+    });
+    return ok ? 0 : -3;
+}
 #endif  // part 2 (cost)
 }
