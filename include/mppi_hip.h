@@ -473,6 +473,22 @@ int mppi_sim_materialise(mppi_ctx_t *ctx, float *dof_dev, float *root_dev, float
  * base - the six floating-base columns are not computed, and the result is refused rather than returned without them. */
 int mppi_sim_jacobian(mppi_ctx_t *ctx, int rb_first, int rb_count, float *jac_dev);  /* [K][rb_count][6][n_dof] */
 int mppi_sim_mass_matrix(mppi_ctx_t *ctx, float *M_dev);                              /* [K][n_dof][n_dof]       */
+/* What joint forces a motion TAKES, at the envs' current joint positions and rates (the state mppi_sim_materialise reports; device
+ * tensors, env-major):
+ *   tau[k] = M(q_k) qdd[k]  (left out when qdd_dev is NULL)  + C(q_k, qd_k) qd_k  (with MPPI_ID_VELOCITY)  + g(q_k)  (with MPPI_ID_GRAVITY)
+ * - the plain rigid-body joint force of the packed model that the step kernels integrate (recursive Newton-Euler): forward dynamics
+ * of that model at (q, qd) under tau gives qdd back.  Gravity is the model's, as the steps take it: an actor with `gravity: false`
+ * has g(q) = 0 exactly.  terms = 0 with a NULL qdd_dev writes exact zeros.
+ * NOT in it: the drives (their implicit kd, h kd, h^2 kp - as they are not in mppi_sim_mass_matrix), joint, effort and velocity
+ * limits, and CONTACT forces - in a contact-scene context the tree is treated as free of contact; add J^T f from the cf tensor.
+ * n_dof is the forest's for a fixed-base forest.  One launch on the context's stream - no allocation, no copy, no synchronise: it
+ * can sit in a captured graph.  qdd_dev and tau_dev must not overlap.
+ * MPPI_EINVAL: a null tau_dev, unknown bits in terms.  MPPI_EUNSUPPORTED (mppi_last_error says so): a robot with a MOVING base
+ * (the six floating-base rows are not computed), a kinematic tree whose launch table lacks the kernel.  Refused before any launch. */
+#define MPPI_ID_GRAVITY   1   /* g(q): the joint forces that hold the robot still                        */
+#define MPPI_ID_VELOCITY  2   /* C(q, qd) qd: centrifugal and Coriolis forces at the envs' joint rates    */
+int mppi_sim_inverse_dynamics(mppi_ctx_t *ctx, const float *qdd_dev /* [K][n_dof] or NULL */, int terms,
+                              float *tau_dev /* [K][n_dof] */);
 int mppi_sim_accumulate_cost(mppi_ctx_t *ctx, int t, const float *cost_dev); /* S += gamma^t c      */
 int mppi_sim_finish(mppi_ctx_t *ctx);                      /* S += control cost                     */
 /* The same horizon in TWO launches for host-side costs that are functions of the state tensors (mppi_isaac.py:57-69 evaluates

@@ -1298,4 +1298,78 @@ MPPI_HD void mass_matrix(M &m0, const Pose<T> &P, const V3 *d, float *Mo) {
     });
 }
 
+// ---- inverse dynamics of one env of a FIXED-base robot (mppi_sim_inverse_dynamics) ----
+enum { kIdGravity = 1, kIdVelocity = 2 };  // MPPI_ID_GRAVITY / MPPI_ID_VELOCITY (include/mppi_hip.h)
+
+// tau [NB] = M(q) qdd (qdd null: left out) + C(q, qd) qd (kIdVelocity) + g(q) (kIdGravity; the model's g, and only if gravity_on) at
+// the body poses P: the plain rigid-body joint forces of the model the step routines integrate - no drive terms, no limits, no
+// contacts.  A recursive Newton-Euler pass in world axes under the rule of mass_matrix: angular velocity, angular acceleration and
+// the acceleration of the body ORIGIN travel from parent to child through the relative offset d[i] only, each body's net force
+// and moment are taken about its own origin p_i (the moment as the rotational part about the centre of mass plus c x f, c = R com)
+// and moved to the parent by d[i] only; nothing is a difference of world positions or a moment about the world origin.
+// Gravity is the base acceleration -g.  tau is linear in (g, qdd) and quadratic in qd, so a part that is not asked for is left
+// out by zeroing its input: the parts of separate calls are the very sums of one call, and with nothing asked for every product
+// has a zero factor.  The outward pass leaves six values per body (F, N) for the inward one.
+template <class T, class M>
+MPPI_HD void inverse_dynamics(M &m0, const Pose<T> &P, const V3 *d, const float *qd, const float *qdd, int terms, float *tau) {
+    constexpr int NB = T::NB;
+    constexpr int NA = NB ? NB : 1;
+    M *mp = &m0;
+    const bool with_g = (terms & kIdGravity) != 0 && m0.gravity_on != 0, with_v = (terms & kIdVelocity) != 0;
+    const V3 zero = {0.f, 0.f, 0.f};
+    const V3 a0 = with_g ? V3{-m0.g[0], -m0.g[1], -m0.g[2]} : zero;
+    V3 w[NA], wd[NA], ao[NA];  // angular velocity, angular acceleration, acceleration of the body origin
+    V3 F[NA], N[NA];           // net force, net moment about p_i
+    static_for<0, NB>([&](auto ic) MPPI_LAMBDA {
+        constexpr int i = ic;
+        constexpr int par = T::par[i];
+        constexpr int pj = par < 0 ? 0 : par;
+        const BodyK1 b = load_block<BodyK1>(launder(mp)->b[i].k1);  // (fetched where it is used, as in mass_matrix)
+        const M3 &R = P.R[i];
+        const V3 az = {R.a[2], R.a[5], R.a[8]};
+        const bool rev = P.jt[i] == 0;
+        const float vi = with_v ? qd[i] : 0.f, ai = qdd != nullptr ? qdd[i] : 0.f;
+        const V3 wp = par < 0 ? zero : w[pj], wdp = par < 0 ? zero : wd[pj], ap = par < 0 ? a0 : ao[pj];
+        const V3 sv = vi * az, sa = ai * az;
+        // the origin rides on the parent at d[i]; a prismatic joint adds its own acceleration and the velocity product 2 w x (qd a)
+        V3 acc = ap + cross(wdp, d[i]) + cross(wp, cross(wp, d[i]));
+        if (!rev) acc = acc + 2.f * cross(wp, sv) + sa;
+        w[i] = rev ? wp + sv : wp;
+        wd[i] = rev ? wdp + sa + cross(wp, sv) : wdp;
+        ao[i] = acc;
+        // f = m a_com = m a_o + wd x h + w x (w x h), h = m c
+        const V3 h = mul(R, V3{b.hb(0), b.hb(1), b.hb(2)});
+        const V3 c = b.invm * h;
+        const V3 f = b.m * acc + cross(wd[i], h) + cross(w[i], cross(w[i], h));
+        // rotational inertia about the centre of mass in world axes: I = R Ic R^T
+        float T9[9];  // R * Ic
+        for (int r = 0; r < 3; r++) {
+            const float r0 = R.a[3 * r], r1 = R.a[3 * r + 1], r2 = R.a[3 * r + 2];
+            T9[3 * r + 0] = r0 * b.Ic(0) + r1 * b.Ic(1) + r2 * b.Ic(2);
+            T9[3 * r + 1] = r0 * b.Ic(1) + r1 * b.Ic(3) + r2 * b.Ic(4);
+            T9[3 * r + 2] = r0 * b.Ic(2) + r1 * b.Ic(4) + r2 * b.Ic(5);
+        }
+        S3 I;
+        I.xx = T9[0] * R.a[0] + T9[1] * R.a[1] + T9[2] * R.a[2];
+        I.xy = T9[0] * R.a[3] + T9[1] * R.a[4] + T9[2] * R.a[5];
+        I.xz = T9[0] * R.a[6] + T9[1] * R.a[7] + T9[2] * R.a[8];
+        I.yy = T9[3] * R.a[3] + T9[4] * R.a[4] + T9[5] * R.a[5];
+        I.yz = T9[3] * R.a[6] + T9[4] * R.a[7] + T9[5] * R.a[8];
+        I.zz = T9[6] * R.a[6] + T9[7] * R.a[7] + T9[8] * R.a[8];
+        F[i] = f;
+        N[i] = mul(I, wd[i]) + cross(w[i], mul(I, w[i])) + cross(c, f);
+    });
+    static_rfor<0, NB>([&](auto ic) MPPI_LAMBDA {
+        constexpr int i = ic;
+        constexpr int par = T::par[i];
+        const V3 az = {P.R[i].a[2], P.R[i].a[5], P.R[i].a[8]};
+        tau[i] = P.jt[i] == 0 ? dot(az, N[i]) : dot(az, F[i]);
+        if constexpr (par >= 0) {  // to the parent's origin: the same force, its moment moved by d[i]
+            constexpr int pj = par < 0 ? 0 : par;
+            N[pj] = N[pj] + N[i] + cross(d[i], F[i]);
+            F[pj] = F[pj] + F[i];
+        }
+    });
+}
+
 }  // namespace mppi

@@ -647,6 +647,7 @@ class IsaacGymWrapper:
         self._state_ptrs = tuple(_dev_ptr(self._state_t[k]) for k in ("dof", "root", "rb", "cf"))
         self._stale, self._needs_reset = True, False
         self._jacobians, self._mass_matrix = {}, None   # acquire_jacobian_tensor / acquire_mass_matrix_tensor: filled by refresh_*()
+        self._bias_force = None                         # acquire_bias_force_tensor: filled by refresh_bias_force_tensors()
         self._visualize_link_present = sc.viz_link_index() >= 0
         self.visualize_link_buffer = []
         if self._visualize_link_present:
@@ -972,11 +973,15 @@ class IsaacGymWrapper:
     # forests: n_dof is the forest's); a moving base raises NotImplementedError with the library's text.  One deviation: the
     # fixed root link keeps its (zero) block, so the Jacobian's link index IS the rigid-body index within the actor (Isaac Gym
     # drops that block and shifts the index by one).
-    def _physics_call(self, fn, *args):
-        """a launch of one of the two entries: per step only, a moving base refused with the library's reason"""
+    def _live_envs_only(self, what="link Jacobians and the mass matrix"):
         if self._state_t is not self._state_t_own:
-            raise PerStepOnly("link Jacobians and the mass matrix are per-step only: they are computed from the live envs, not from the "
+            raise PerStepOnly(f"{what} are per-step only: they are computed from the live envs, not from the "
                               "precomputed states of a planner's horizon view")
+
+    def _physics_call(self, fn, *args, what="link Jacobians and the mass matrix"):
+        """a launch of one of the physics entries: per step only (`what` is refused on a horizon view), a moving base refused with
+        the library's reason"""
+        self._live_envs_only(what)
         self._reset_envs_if_needed()
         rc = fn(self._ctx, *args)
         if rc == capi.MPPI_EUNSUPPORTED:
@@ -1018,6 +1023,44 @@ class IsaacGymWrapper:
         rb = self.scene.rigid_body_index(actor_name, link_name)
         out = torch.empty((self.num_envs, 6, self.scene.n_dof), dtype=torch.float32, device=self.device)
         self._physics_call(self._lib.mppi_sim_jacobian, rb, 1, _dev_ptr(out))
+        return out
+
+    # ------------------------------------------------------------------ inverse dynamics and bias forces
+    # What joint forces a motion takes: tau = M(q) qdd + C(q, qd) qd + g(q) of every env at its current joint positions and rates
+    # (mppi_sim_inverse_dynamics: the rigid-body model the step integrates - no drive terms, no limits, no contact forces; gravity
+    # as the robot's actor file switches it).  Fixed-base robots and fixed-base forests, as for the Jacobians.
+    _ID_WHAT = "inverse dynamics and bias forces"
+
+    def acquire_bias_force_tensor(self, actor_name: str):
+        """[K, n_dof]: C(q, qd) qd + g(q) of every env - what the joints must push to keep their rates.  Zero until
+        refresh_bias_force_tensors()."""
+        self._live_envs_only(self._ID_WHAT)
+        self.scene.actor_index(actor_name)
+        if self._bias_force is None:
+            self._bias_force = torch.zeros((self.num_envs, self.scene.n_dof), dtype=torch.float32, device=self.device)
+        return self._bias_force
+
+    def refresh_bias_force_tensors(self) -> None:
+        self._live_envs_only(self._ID_WHAT)
+        if self._bias_force is not None:
+            self._physics_call(self._lib.mppi_sim_inverse_dynamics, None, capi.ID_GRAVITY | capi.ID_VELOCITY, _dev_ptr(self._bias_force),
+                               what=self._ID_WHAT)
+
+    def inverse_dynamics(self, qdd=None, gravity=True, velocity=True):
+        """a fresh [K, n_dof] tensor tau = M(q) qdd (qdd None: left out) + C(q, qd) qd (velocity) + g(q) (gravity).  qdd: [n_dof],
+        the same acceleration for every env, or [K, n_dof]."""
+        self._live_envs_only(self._ID_WHAT)
+        K, n = self.num_envs, self.scene.n_dof
+        if qdd is not None:
+            qdd = torch.as_tensor(qdd, dtype=torch.float32, device=self.device)
+            if tuple(qdd.shape) == (n,):
+                qdd = qdd.expand(K, n)
+            elif tuple(qdd.shape) != (K, n):
+                raise ValueError(f"qdd has shape {tuple(qdd.shape)}: expected [{n}] or [{K}, {n}]")
+            qdd = qdd.contiguous()
+        out = torch.empty((K, n), dtype=torch.float32, device=self.device)
+        terms = (capi.ID_GRAVITY if gravity else 0) | (capi.ID_VELOCITY if velocity else 0)
+        self._physics_call(self._lib.mppi_sim_inverse_dynamics, _dev_ptr(qdd), terms, _dev_ptr(out), what=self._ID_WHAT)
         return out
 
     # ------------------------------------------------------------------ env mutation (reference :423-427, :695-758)
