@@ -489,6 +489,20 @@ int mppi_sim_mass_matrix(mppi_ctx_t *ctx, float *M_dev);                        
 #define MPPI_ID_VELOCITY  2   /* C(q, qd) qd: centrifugal and Coriolis forces at the envs' joint rates    */
 int mppi_sim_inverse_dynamics(mppi_ctx_t *ctx, const float *qdd_dev /* [K][n_dof] or NULL */, int terms,
                               float *tau_dev /* [K][n_dof] */);
+/* What acceleration a joint force GIVES, at the envs' current joint positions and rates - the question above in the other direction:
+ *   qdd[k] = M(q_k)^-1 ( tau[k]  (zero when tau_dev is NULL)  - C(q_k, qd_k) qd_k  (with MPPI_ID_VELOCITY)  - g(q_k)  (with MPPI_ID_GRAVITY) )
+ * - forward dynamics of the same plain rigid-body model, by an articulated-body solve in O(n_dof): no matrix is formed or factored.
+ * mppi_sim_inverse_dynamics of the result gives tau back.  terms = 0 on a unit torque e_i gives column i of M^-1; terms = 0 with a
+ * NULL tau_dev writes exact zeros; both terms with a NULL tau_dev give the acceleration of the joints left to themselves.
+ * NOT in it, as above: the drives (kd, h kd, h^2 kp), joint, effort and velocity limits, and CONTACT forces - in a contact-scene
+ * context the tree is treated as free of contact.  Gravity is the model's, as the steps take it.
+ * n_dof is the forest's for a fixed-base forest.  One launch on the context's stream - no allocation, no copy, no synchronise: it
+ * can sit in a captured graph.  tau_dev and qdd_dev must not overlap.
+ * MPPI_EINVAL: a null qdd_dev, unknown bits in terms.  MPPI_EUNSUPPORTED (mppi_last_error says so): a robot with a MOVING base
+ * (the six floating-base accelerations are not solved for), a kinematic tree whose launch table lacks the kernel.  Refused before
+ * any launch. */
+int mppi_sim_forward_dynamics(mppi_ctx_t *ctx, const float *tau_dev /* [K][n_dof] or NULL */, int terms,
+                              float *qdd_dev /* [K][n_dof] */);
 int mppi_sim_accumulate_cost(mppi_ctx_t *ctx, int t, const float *cost_dev); /* S += gamma^t c      */
 int mppi_sim_finish(mppi_ctx_t *ctx);                      /* S += control cost                     */
 /* The same horizon in TWO launches for host-side costs that are functions of the state tensors (mppi_isaac.py:57-69 evaluates

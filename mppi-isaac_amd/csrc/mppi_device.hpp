@@ -1372,4 +1372,143 @@ MPPI_HD void inverse_dynamics(M &m0, const Pose<T> &P, const V3 *d, const float 
     });
 }
 
+// ---- forward dynamics of one env of a FIXED-base robot (mppi_sim_forward_dynamics) ----
+// the articulated inertia A and bias wrench p of a body, both about the body's origin p_i, as seen from the PARENT's origin
+// p_i - dd:  X^T A X and X^T p  with  X (wd, a) = (wd, a + wd x dd).  With Dx = [dd]x:
+//   M' = M,   H' = H + Dx M,   I' = I + Dx H^T + (Dx H'^T)^T   (= I - H Dx + Dx H^T - Dx M Dx),   n' = n + dd x f,  f' = f.
+// A rigid body's H = [h]x, M = m 1 give back the rule of mass_matrix: h' = h + m dd.
+MPPI_HD void shift_to_parent(AI &A, SV &p, V3 dd) {
+    const V3 m0 = cross(dd, V3{A.M.xx, A.M.xy, A.M.xz}), m1 = cross(dd, V3{A.M.xy, A.M.yy, A.M.yz}), m2 = cross(dd, V3{A.M.xz, A.M.yz, A.M.zz});
+    // column j of Dx H^T: dd x (row j of H), of the inertia as it stands
+    const V3 a0 = cross(dd, V3{A.H[0], A.H[1], A.H[2]}), a1 = cross(dd, V3{A.H[3], A.H[4], A.H[5]}), a2 = cross(dd, V3{A.H[6], A.H[7], A.H[8]});
+    A.H[0] += m0.x; A.H[1] += m1.x; A.H[2] += m2.x;
+    A.H[3] += m0.y; A.H[4] += m1.y; A.H[5] += m2.y;
+    A.H[6] += m0.z; A.H[7] += m1.z; A.H[8] += m2.z;
+    // ... and of the shifted one
+    const V3 b0 = cross(dd, V3{A.H[0], A.H[1], A.H[2]}), b1 = cross(dd, V3{A.H[3], A.H[4], A.H[5]}), b2 = cross(dd, V3{A.H[6], A.H[7], A.H[8]});
+    A.I.xx += a0.x + b0.x;
+    A.I.xy += a1.x + b0.y;
+    A.I.xz += a2.x + b0.z;
+    A.I.yy += a1.y + b1.y;
+    A.I.yz += a2.y + b1.z;
+    A.I.zz += a2.z + b2.z;
+    p.a = p.a + cross(dd, p.l);
+}
+
+// qdd [NB] = M(q)^-1 (tau (null: zero) - C(q, qd) qd (kIdVelocity) - g(q) (kIdGravity; the model's g, and only if gravity_on)) at the
+// body poses P: forward dynamics of the plain rigid-body model of inverse_dynamics - no drive terms, no limits, no contacts.  A
+// three-pass articulated-body solve in world axes under the rule of mass_matrix: the articulated inertia (symmetric I, general H,
+// symmetric M once a joint's rank-1 term is gone) and the bias wrench (moment n, force f) of body i are carried about ITS OWN
+// origin p_i and moved to the parent by the relative offset d[i] only (shift_to_parent) - aba_world, about the world origin, adds
+// them.  Motion is what inverse_dynamics carries: angular velocity, angular acceleration and the acceleration of the body
+// origin, so that a child's acceleration is  X (wd_p, a_p) + c + S qdd  with the velocity products c = (w_p x qd a, w_p x (w_p x d))
+// of a revolute joint, (0, w_p x (w_p x d) + 2 w_p x qd a) of a prismatic one, and a body's bias wrench is (w x I w, w x (w x h)).
+// A part that is not asked for is left out by zeroing its input (qd -> 0, the base acceleration -> 0), as there: the result with
+// qd = 0 is the result without kIdVelocity bit for bit, and with nothing asked for and no tau every product has a zero factor.
+template <class T, class M>
+MPPI_HD void forward_dynamics(M &m0, const Pose<T> &P, const V3 *d, const float *qd, const float *tau, int terms, float *qdd) {
+    constexpr int NB = T::NB;
+    constexpr int NA = NB ? NB : 1;
+    M *mp = &m0;
+    const bool with_g = (terms & kIdGravity) != 0 && m0.gravity_on != 0, with_v = (terms & kIdVelocity) != 0;
+    const V3 zero = {0.f, 0.f, 0.f};
+    const V3 a0 = with_g ? V3{-m0.g[0], -m0.g[1], -m0.g[2]} : zero;
+    V3 w[NA];                // angular velocity
+    SV U[NA];                // A S: (moment about p_i, force)
+    float invd[NA], u[NA];   // 1 / (S^T A S),  tau - S^T p
+    AI accA[NA];             // the children's articulated inertias and bias wrenches, about the parent's origin
+    SV accp[NA];
+    // pass 1: angular velocities, base to leaves
+    static_for<0, NB>([&](auto ic) MPPI_LAMBDA {
+        constexpr int i = ic;
+        constexpr int par = T::par[i];
+        constexpr int pj = par < 0 ? 0 : par;
+        const V3 az = {P.R[i].a[2], P.R[i].a[5], P.R[i].a[8]};
+        const float vi = with_v ? qd[i] : 0.f;
+        const V3 wp = par < 0 ? zero : w[pj];
+        w[i] = P.jt[i] == 0 ? wp + vi * az : wp;
+    });
+    // pass 2: articulated inertias and bias wrenches, leaves to base
+    static_rfor<0, NB>([&](auto ic) MPPI_LAMBDA {
+        constexpr int i = ic;
+        constexpr int par = T::par[i];
+        const BodyK1 b = load_block<BodyK1>(launder(mp)->b[i].k1);  // (fetched where it is used, as in mass_matrix)
+        const M3 &R = P.R[i];
+        const V3 az = {R.a[2], R.a[5], R.a[8]};
+        const bool rev = P.jt[i] == 0;
+        // the body's own inertia about p_i: I = R Ic R^T + m (|c|^2 1 - c c^T), H = [h]x, h = m c, c = R com
+        const V3 h = mul(R, V3{b.hb(0), b.hb(1), b.hb(2)});
+        float T9[9];  // R * Ic
+        for (int r = 0; r < 3; r++) {
+            const float r0 = R.a[3 * r], r1 = R.a[3 * r + 1], r2 = R.a[3 * r + 2];
+            T9[3 * r + 0] = r0 * b.Ic(0) + r1 * b.Ic(1) + r2 * b.Ic(2);
+            T9[3 * r + 1] = r0 * b.Ic(1) + r1 * b.Ic(3) + r2 * b.Ic(4);
+            T9[3 * r + 2] = r0 * b.Ic(2) + r1 * b.Ic(4) + r2 * b.Ic(5);
+        }
+        const V3 c = b.invm * h;
+        const float hh = dot(h, c);
+        AI A;
+        A.I.xx = T9[0] * R.a[0] + T9[1] * R.a[1] + T9[2] * R.a[2] + hh - h.x * c.x;
+        A.I.xy = T9[0] * R.a[3] + T9[1] * R.a[4] + T9[2] * R.a[5] - h.x * c.y;
+        A.I.xz = T9[0] * R.a[6] + T9[1] * R.a[7] + T9[2] * R.a[8] - h.x * c.z;
+        A.I.yy = T9[3] * R.a[3] + T9[4] * R.a[4] + T9[5] * R.a[5] + hh - h.y * c.y;
+        A.I.yz = T9[3] * R.a[6] + T9[4] * R.a[7] + T9[5] * R.a[8] - h.y * c.z;
+        A.I.zz = T9[6] * R.a[6] + T9[7] * R.a[7] + T9[8] * R.a[8] + hh - h.z * c.z;
+        A.H[0] = 0.f;  A.H[1] = -h.z; A.H[2] = h.y;
+        A.H[3] = h.z;  A.H[4] = 0.f;  A.H[5] = -h.x;
+        A.H[6] = -h.y; A.H[7] = h.x;  A.H[8] = 0.f;
+        A.M = {b.m, 0.f, 0.f, b.m, 0.f, b.m};
+        // the rigid body's bias wrench about p_i
+        const V3 wi = w[i];
+        SV p = {cross(wi, mul(A.I, wi)), cross(wi, cross(wi, h))};
+        if constexpr (last_child<T>(i) >= 0) {  // the subtrees below, already about p_i
+            add_to(A, accA[i]);
+            p = p + accp[i];
+        }
+        const SV S = rev ? SV{az, zero} : SV{zero, az};
+        U[i] = mul(A, S);
+        invd[i] = frcp(dot(S, U[i]));
+        u[i] = (tau != nullptr ? tau[i] : 0.f) - dot(S, p);
+        if constexpr (par >= 0) {
+            // what the parent sees of this subtree with joint i left free:  A - U U^T / D,  p + (A - U U^T / D) c + U u / D
+            constexpr int pj = par < 0 ? 0 : par;
+            const V3 wp = w[pj];
+            const V3 sv = (with_v ? qd[i] : 0.f) * az;
+            const V3 cen = cross(wp, cross(wp, d[i]));
+            const SV cv = rev ? SV{cross(wp, sv), cen} : SV{zero, cen + 2.f * cross(wp, sv)};
+            rank1_sub(A, U[i], invd[i]);
+            const SV Ac = mul(A, cv);
+            const float k = u[i] * invd[i];
+            SV pa = {p.a + Ac.a + k * U[i].a, p.l + Ac.l + k * U[i].l};
+            shift_to_parent(A, pa, d[i]);
+            if constexpr (last_child<T>(pj) == i) {
+                accA[pj] = A;
+                accp[pj] = pa;
+            } else {
+                add_to(accA[pj], A);
+                accp[pj] = accp[pj] + pa;
+            }
+        }
+    });
+    // pass 3: accelerations, base to leaves.  Gravity is the base acceleration -g.
+    V3 wd[NA], ao[NA];  // angular acceleration, acceleration of the body origin
+    static_for<0, NB>([&](auto ic) MPPI_LAMBDA {
+        constexpr int i = ic;
+        constexpr int par = T::par[i];
+        constexpr int pj = par < 0 ? 0 : par;
+        const V3 az = {P.R[i].a[2], P.R[i].a[5], P.R[i].a[8]};
+        const bool rev = P.jt[i] == 0;
+        const V3 wp = par < 0 ? zero : w[pj], wdp = par < 0 ? zero : wd[pj], ap = par < 0 ? a0 : ao[pj];
+        const V3 sv = (with_v ? qd[i] : 0.f) * az;
+        // the origin rides on the parent at d[i]; the joint's velocity products, as in inverse_dynamics
+        V3 acc = ap + cross(wdp, d[i]) + cross(wp, cross(wp, d[i]));
+        if (!rev) acc = acc + 2.f * cross(wp, sv);
+        const V3 ang = rev ? wdp + cross(wp, sv) : wdp;
+        const float dd = (u[i] - dot(U[i], SV{ang, acc})) * invd[i];
+        qdd[i] = dd;
+        wd[i] = rev ? ang + dd * az : ang;
+        ao[i] = rev ? acc : acc + dd * az;
+    });
+}
+
 }  // namespace mppi

@@ -1387,6 +1387,19 @@ int mppi_sim_inverse_dynamics(mppi_ctx_t *c, const float *qdd_dev, int terms, fl
     e->sim_inverse_dynamics(c, qdd_dev, terms, tau_dev);
     return launch_check();
 }
+/* the accelerations a joint force gives, at the envs' current joint positions and rates: one launch on the context's stream, no
+ * allocation, no copy, no synchronise (include/mppi_hip.h) */
+int mppi_sim_forward_dynamics(mppi_ctx_t *c, const float *tau_dev, int terms, float *qdd_dev) {
+    CTX_TRY(c);
+    if (!qdd_dev) return fail(MPPI_EINVAL, "mppi_sim_forward_dynamics: null output");
+    if (terms & ~(MPPI_ID_GRAVITY | MPPI_ID_VELOCITY))
+        return fail(MPPI_EINVAL, "mppi_sim_forward_dynamics: unknown bits in terms = " + std::to_string(terms) + " (MPPI_ID_GRAVITY | MPPI_ID_VELOCITY)");
+    const TopoEntry *e = nullptr;
+    if (int rc = physics_entry(c, "mppi_sim_forward_dynamics", e)) return rc;
+    if (!e->sim_forward_dynamics) return fail(MPPI_EUNSUPPORTED, "mppi_sim_forward_dynamics: not available for this kinematic tree");
+    e->sim_forward_dynamics(c, tau_dev, terms, qdd_dev);
+    return launch_check();
+}
 int mppi_sim_accumulate_cost(mppi_ctx_t *c, int t, const float *cost_dev) {
     CTX_TRY(c);
     if (!cost_dev) return fail(MPPI_EINVAL, "null cost");

@@ -1866,6 +1866,42 @@ __global__ __launch_bounds__(kWave) void k_sim_inverse_dynamics(const DevModel *
     __syncthreads();
     store_staged_rows<kLen>(s_row, n_rows, out + (size_t)k0 * kLen, kLen);
 }
+// qdd [K][n] = M(q)^-1 (tau ([K][n], null: zero) - C(q, qd) qd - g(q) as `terms` asks) (forward_dynamics, mppi_device.hpp) at the envs'
+// current joint positions and rates: the mirror image of k_sim_inverse_dynamics, through the same tile with the same two barriers.
+// Rows past K - 1 of the last wavefront are neither loaded nor stored.
+template <class T>
+__global__ __launch_bounds__(kWave) void k_sim_forward_dynamics(const DevModel *__restrict__ m, int K, const float *__restrict__ x0_root,
+                                                                const float *__restrict__ q_, const float *__restrict__ qd_,
+                                                                const float *__restrict__ base_, const float *__restrict__ tau_, int terms,
+                                                                float *__restrict__ out) {
+    constexpr int NB = T::NB, kLen = NB, kStride = staged_stride(kLen);
+    __shared__ float s_row[kWave * kStride];
+    CModel &M = *(CModel *)m;
+    const int k0 = blockIdx.x * kWave, k = k0 + threadIdx.x;
+    const int n_rows = K - k0 < kWave ? K - k0 : kWave;
+    if (tau_ != nullptr) {
+        load_staged_rows<kLen>(s_row, n_rows, tau_ + (size_t)k0 * kLen, kLen);
+        __syncthreads();
+    }
+    if (k < K) {
+        Pose<T> P;
+        V3 d[NB ? NB : 1];
+        float qd[NB ? NB : 1], tau[NB ? NB : 1], qdd[NB ? NB : 1];
+        sim_env_pose<T>(M, K, k, x0_root, q_, base_, P, d);
+        static_for<0, NB>([&](auto ic) {
+            constexpr int i = ic;
+            qd[i] = qd_[(size_t)i * K + k];
+            tau[i] = tau_ != nullptr ? s_row[threadIdx.x * kStride + i] : 0.f;
+        });
+        forward_dynamics<T>(M, P, d, qd, tau, terms, qdd);  // (tau left out: a zero row - the same sums; a pointer chosen at run time would keep the rows in scratch)
+        static_for<0, NB>([&](auto ic) {
+            constexpr int i = ic;
+            s_row[threadIdx.x * kStride + i] = qdd[i];
+        });
+    }
+    __syncthreads();
+    store_staged_rows<kLen>(s_row, n_rows, out + (size_t)k0 * kLen, kLen);
+}
 
 // Parity / debug entry (mppi_eval_cost): the cost program of the context evaluated by the interpreter the rollout kernels run
 // (program_cost_with, mppi_device.hpp) on CALLER-GIVEN simulator answers - reference-layout rows of n envs - instead of the
@@ -2059,6 +2095,7 @@ struct TopoEntry {
     void (*sim_jacobian)(mppi_ctx *, int, int, float *);  // mppi_sim_jacobian (null: not built for this tree)
     void (*sim_mass_matrix)(mppi_ctx *, float *);         // mppi_sim_mass_matrix
     void (*sim_inverse_dynamics)(mppi_ctx *, const float *, int, float *);  // mppi_sim_inverse_dynamics
+    void (*sim_forward_dynamics)(mppi_ctx *, const float *, int, float *);  // mppi_sim_forward_dynamics
     hipError_t (*raise_lds)(size_t, size_t);
     size_t (*static_lds)();  // largest static __shared__ footprint among the contact-scene kernels (counts against the 160 KiB too)
 };
@@ -2246,6 +2283,11 @@ void launch_sim_inverse_dynamics_t(mppi_ctx *c, const float *qdd, int terms, flo
                        c->scene ? c->d_base : nullptr, qdd, terms, out);
 }
 template <class T>
+void launch_sim_forward_dynamics_t(mppi_ctx *c, const float *tau, int terms, float *out) {
+    hipLaunchKernelGGL(k_sim_forward_dynamics<T>, dim3(c->n_waves), dim3(kWave), 0, c->stream, c->d_model, c->K, c->d_x0_root, c->d_q, c->d_qd,
+                       c->scene ? c->d_base : nullptr, tau, terms, out);
+}
+template <class T>
 void launch_rollout_t(mppi_ctx *c) { launch_rollout_kernel(k_rollout<T>, c->n_waves, kWave, 0, c); }
 template <class T>
 void launch_sim_step_t(mppi_ctx *c, int mode, int t, const float *u_ext) {
@@ -2284,10 +2326,11 @@ void fill_topo_entry_free(TopoEntry &e) {
     e.materialise = &launch_materialise_t<T>;
     e.combine_world = &launch_combine_world_t<T>;
     e.eval_cost = &launch_eval_cost_t<T>;
-    if constexpr (T::NBASE == 1) {  // (forests of several moving bases are refused by all three entries: nothing to launch)
+    if constexpr (T::NBASE == 1) {  // (forests of several moving bases are refused by all four entries: nothing to launch)
         e.sim_jacobian = &launch_sim_jacobian_t<T>;
         e.sim_mass_matrix = &launch_sim_mass_matrix_t<T>;
         e.sim_inverse_dynamics = &launch_sim_inverse_dynamics_t<T>;
+        e.sim_forward_dynamics = &launch_sim_forward_dynamics_t<T>;
     }
 }
 template <class T>

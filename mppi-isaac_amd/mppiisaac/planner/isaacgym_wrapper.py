@@ -648,6 +648,7 @@ class IsaacGymWrapper:
         self._stale, self._needs_reset = True, False
         self._jacobians, self._mass_matrix = {}, None   # acquire_jacobian_tensor / acquire_mass_matrix_tensor: filled by refresh_*()
         self._bias_force = None                         # acquire_bias_force_tensor: filled by refresh_bias_force_tensors()
+        self._free_acceleration = None                  # acquire_free_acceleration_tensor: filled by refresh_free_acceleration_tensors()
         self._visualize_link_present = sc.viz_link_index() >= 0
         self.visualize_link_buffer = []
         if self._visualize_link_present:
@@ -1062,6 +1063,56 @@ class IsaacGymWrapper:
         terms = (capi.ID_GRAVITY if gravity else 0) | (capi.ID_VELOCITY if velocity else 0)
         self._physics_call(self._lib.mppi_sim_inverse_dynamics, _dev_ptr(qdd), terms, _dev_ptr(out), what=self._ID_WHAT)
         return out
+
+    # ------------------------------------------------------------------ forward dynamics, free acceleration and M^-1
+    # What acceleration a joint force gives: qdd = M(q)^-1 (tau - C(q, qd) qd - g(q)) of every env at its current joint positions and
+    # rates (mppi_sim_forward_dynamics: an articulated-body solve of the model of inverse_dynamics - no drive terms, no limits, no
+    # contact forces).  Fixed-base robots and fixed-base forests, as for the Jacobians.
+    _FD_WHAT = "forward dynamics and free accelerations"
+
+    def forward_dynamics(self, tau=None, gravity=True, velocity=True):
+        """a fresh [K, n_dof] tensor qdd = M(q)^-1 (tau (None: zero) - C(q, qd) qd (velocity) - g(q) (gravity)).  tau: [n_dof], the
+        same joint force for every env, or [K, n_dof]."""
+        self._live_envs_only(self._FD_WHAT)
+        K, n = self.num_envs, self.scene.n_dof
+        if tau is not None:
+            tau = torch.as_tensor(tau, dtype=torch.float32, device=self.device)
+            if tuple(tau.shape) == (n,):
+                tau = tau.expand(K, n)
+            elif tuple(tau.shape) != (K, n):
+                raise ValueError(f"tau has shape {tuple(tau.shape)}: expected [{n}] or [{K}, {n}]")
+            tau = tau.contiguous()
+        out = torch.empty((K, n), dtype=torch.float32, device=self.device)
+        terms = (capi.ID_GRAVITY if gravity else 0) | (capi.ID_VELOCITY if velocity else 0)
+        self._physics_call(self._lib.mppi_sim_forward_dynamics, _dev_ptr(tau), terms, _dev_ptr(out), what=self._FD_WHAT)
+        return out
+
+    def acquire_free_acceleration_tensor(self, actor_name: str):
+        """[K, n_dof]: -M(q)^-1 (C(q, qd) qd + g(q)) of every env - how the joints accelerate when nothing pushes them: the
+        counterpart of the bias forces.  Zero until refresh_free_acceleration_tensors()."""
+        self._live_envs_only(self._FD_WHAT)
+        self.scene.actor_index(actor_name)
+        if self._free_acceleration is None:
+            self._free_acceleration = torch.zeros((self.num_envs, self.scene.n_dof), dtype=torch.float32, device=self.device)
+        return self._free_acceleration
+
+    def refresh_free_acceleration_tensors(self) -> None:
+        self._live_envs_only(self._FD_WHAT)
+        if self._free_acceleration is not None:
+            self._physics_call(self._lib.mppi_sim_forward_dynamics, None, capi.ID_GRAVITY | capi.ID_VELOCITY, _dev_ptr(self._free_acceleration),
+                               what=self._FD_WHAT)
+
+    def inverse_mass_matrix(self):
+        """a fresh [K, n_dof, n_dof] tensor M(q)^-1 of every env: n_dof launches on the unit torques with neither gravity nor
+        velocity terms.  Written symmetric from the lower triangle, so it is symmetric bit for bit like M."""
+        self._live_envs_only(self._FD_WHAT)
+        K, n = self.num_envs, self.scene.n_dof
+        cols = torch.empty((n, K, n), dtype=torch.float32, device=self.device)      # cols[i, k, :] = M^-1 e_i of env k
+        units = torch.eye(n, dtype=torch.float32, device=self.device)[:, None, :].expand(n, K, n).contiguous()
+        for i in range(n):
+            self._physics_call(self._lib.mppi_sim_forward_dynamics, _dev_ptr(units[i]), 0, _dev_ptr(cols[i]), what=self._FD_WHAT)
+        low = torch.tril(cols.permute(1, 2, 0))      # [K, row, column]
+        return low + torch.tril(low, -1).transpose(1, 2)
 
     # ------------------------------------------------------------------ env mutation (reference :423-427, :695-758)
     def _restart(self):
