@@ -803,6 +803,14 @@ MPPI_HD void step(CModel &m0, const float *root, float *q, float *qd, const floa
         const float h = m.h, kp = pos ? m.kp : 0.f, kd = m.kd + h * kp;
         Pose<T> P;
         forward_kinematics<T>(m, root, q, P);
+        // (the position drive's implicit damping, (kd + h kp) h = 0.05 at the shipped gains, hides the cancellation in S^T I^A S
+        // about the world origin as little as a drive held at its limit does: every solve of a position-driven step is taken
+        // about the last body's origin - see the second solve below)
+        if constexpr (NB > 0)
+            if (pos) {
+                const V3 org = P.p[NB - 1];
+                static_for<0, NB>([&](auto ic) MPPI_LAMBDA { P.p[ic] = P.p[ic] - org; });
+            }
         float tau[NB], kdh[NB], qdd[NB], ff[NB], vs[NB];
         static_for<0, NB>([&](auto ic) MPPI_LAMBDA {
             constexpr int i = ic;

@@ -755,6 +755,14 @@ MPPI_HD void quad_step(M &m0, QPose<T, JT> &P, QF *q, QF *qd, const QF *target, 
                 kd += h * kp;
                 static_for<0, NB>([&](auto ic) MPPI_LAMBDA { tau[ic] = kp * (target[ic] - q[ic]) - kd * qd[ic]; });
                 driven = true;
+                // (its implicit damping, (kd + h kp) h = 0.05 at the shipped gains, hides the cancellation about the world
+                // origin as little as a drive held at its limit: both solves of a position-driven substep are taken about the
+                // last body's origin - see the second solve below.  Quad AND octet layout: the generic instantiation of the
+                // octet kernels holds the quad's pose rows in both halves of the octet, and P is rebuilt from the base pose below)
+                if constexpr (NB > 0) {
+                    const QF org = P.pos(NB - 1);
+                    static_for<0, NB>([&](auto ic) MPPI_LAMBDA { P.R2p[ic].y = P.R2p[ic].y - org; });
+                }
             }
         if (!driven) {
             if (m.drive_mode == kDriveVelocity) {

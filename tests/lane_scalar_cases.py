@@ -104,8 +104,9 @@ def path_counts(m, q, qd):
     return int(at_stop.sum()), int(at_vmax.sum())
 
 
-def oracle_paths(o, m, cfg, cost, dof, root, U, eps):
-    """the same rollout on the CPU oracle `o`: (q, qd) [H][n][K] after every step and the saturation sets [K][H * substeps]"""
+def oracle_paths(o, m, cfg, cost, dof, root, U, eps, prior=None):
+    """the same rollout on the CPU oracle `o`: (q, qd) [H][n][K] after every step and the saturation sets [K][H * substeps]
+    (`prior`: the sequence the sample before the last takes under use_priors; its saturation set is the noise sample's)"""
     K, H, nu, n = cfg.num_samples, cfg.horizon, cfg.nu, m.n_bodies
     lo, hi = np.array([cfg.u_min[c] for c in range(nu)]), np.array([cfg.u_max[c] for c in range(nu)])
     q, qd = np.zeros((H, n, K)), np.zeros((H, n, K))
@@ -117,6 +118,8 @@ def oracle_paths(o, m, cfg, cost, dof, root, U, eps):
             u = np.asarray(U[t], np.float64) + eps[t, :, k]
             if cfg.sample_null_action and cfg.k_offset + k == cfg.k_total - 1:
                 u = np.zeros(nu)
+            if prior is not None and cfg.use_priors and cfg.k_offset + k == cfg.k_total - 2:
+                u = np.asarray(prior[t], np.float64)
             x, v = o.step(m, root, x, v, o.cmd_map(m, np.clip(u, lo, hi)))
             q[t, :, k], qd[t, :, k] = x, v
         o.lib.orc_rollout_satlog(C.byref(m), C.byref(cfg), C.byref(cost), o.p(o.arr(dof)), o.p(o.arr(root)), o.p(o.arr(U)), o.p(o.arr(eps)),

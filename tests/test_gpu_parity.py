@@ -983,7 +983,7 @@ JACKAL_WHEELS = {"left_wheel_joints": ["front_left_wheel", "rear_left_wheel"], "
 
 
 @pytest.mark.parametrize("actors,init,link,nu,sigma,umax,over", [
-    (["omnipanda_effort", "goal"], [[0.0, 0.0, 0.0]], "panda_hand", 12, 4.0, 10.0, None),   # effort mode, 12-DoF tree, quad kernel
+    (["omnipanda_effort", "goal"], [[0.0, 0.0, 0.0]], "panda_hand", 12, 4.0, 10.0, None),   # effort mode, 12-DoF tree
     (["heijn", "goal"], [[0.0, 0.0, 0.0]], "front_link", 3, 1.0, 1.5, None),                 # holonomic base
     (["albert", "goal"], [[0.0, 0.0, 0.2]], "mmrobot_link7", 9, 0.2, 0.5, None),            # diff-drive base + arm: contact scene
     (["jackal", "goal"], [[0.0, 0.0, 0.1]], "base_link", 2, 0.5, 1.0, JACKAL_WHEELS),       # 4-wheel skid steer: contact scene
@@ -991,12 +991,15 @@ JACKAL_WHEELS = {"left_wheel_joints": ["front_left_wheel", "rear_left_wheel"], "
     (["omnipanda", "goal"], [[0.0, 0.0, 0.0]], "panda_hand", 12, 0.2, 0.5, None),           # velocity mode, holonomic base + arm + gripper
     (["anymal", "goal"], [[0.0, 0.0, 0.62]], "base", 12, 1.0, 5.5, None),                     # quadruped on its feet: floating trunk, four legs
     # dof_mode "position" (reference isaacgym_wrapper.py:501-504,571-572: the command overwrites the DOF state, stiffness drive):
-    (["panda_stick", "goal"], [[0.0, 0.0, 0.0]], "panda_ee_tip", 7, 0.05, 2.5, {"dof_mode": "position"}),   # quad kernel
+    (["panda_stick", "goal"], [[0.0, 0.0, 0.0]], "panda_ee_tip", 7, 0.05, 2.5, {"dof_mode": "position"}),   # 7-body chain (generic instantiation)
     (["panda_gripper", "goal"], [[0.0, 0.0, 0.0]], "panda_hand", 9, 0.02, 2.5, {"dof_mode": "position"}),   # 9-body tree
-    (["albert", "goal"], [[0.0, 0.0, 0.2]], "mmrobot_link7", 9, 0.05, 2.5, {"dof_mode": "position"}),       # contact scene (octet kernel)
+    (["albert", "goal"], [[0.0, 0.0, 0.2]], "mmrobot_link7", 9, 0.05, 2.5, {"dof_mode": "position"}),       # contact scene
 ])
 def test_more_robots_rollout(actors, init, link, nu, sigma, umax, over, lib, oracle64):
-    """SURVEY 8f rank 1 robots through the HIP path: reach cost on one of their links, rollouts vs the oracle."""
+    """SURVEY 8f rank 1 robots through the HIP path: reach cost on one of their links, rollouts vs the oracle.  The kernel that
+    mppi_create selects at K = 128, H = 12 is asserted by name (csrc/mppi_hip.hip): `oct-pair` for every contact-free tree (eight
+    workgroups, a horizon within the control table), `scene-oct-pair` for contact scenes of at most four bodies and 64 candidate
+    pairs, `scene-oct` for the others.  (Every layout of the contact-free trees: tests/test_gpu_tree_matrix.py.)"""
     from mppiisaac.planner.mppi import MPPIConfig, make_config
     from scenes import build_scene
     scene = build_scene(actors, init, robot_overrides=over)
@@ -1013,6 +1016,10 @@ def test_more_robots_rollout(actors, init, link, nu, sigma, umax, over, lib, ora
     dof, root = scene.initial_state()
     root[scene.actor_index("goal"), 0:3] = [0.6, 0.3, 0.5]
     c = Ctx(m, cfg, cost)
+    info = C.create_string_buffer(256)
+    c.call("mppi_kernel_info", info, 256)
+    kernel = "oct-pair" if not oracle64.is_scene(m) else ("scene-oct-pair" if m.n_bodies <= 4 and m.n_pairs <= 64 else "scene-oct")
+    assert f"rollout={kernel} ".encode() in info.value, (kernel, info.value)
     c.call("mppi_sample", C.c_uint32(0))
     eps = c.get("mppi_get_noise", (H, nu, K))
     c.set_state(dof, root)

@@ -311,8 +311,10 @@ def run_gpu(lib, b, kernel, cus):
     return name, np.concatenate([g.eps for g in gs], axis=2), [out]
 
 
-def compare(tag, got, want, umax):
-    """prints the measured maxima next to the tolerances, then asserts; -> the list of failures"""
+def compare(tag, got, want, umax, tol=None):
+    """prints the measured maxima next to the tolerances (TOL, or the table `tol` of a module that measured its own), then
+    asserts; -> the list of failures"""
+    tols = TOL if tol is None else tol
     fails, cells = [], []
     for key in ("S", "du", "viz", "U", "action", "beta_eta"):
         if want[key] is None:
@@ -320,9 +322,9 @@ def compare(tag, got, want, umax):
         g, w = got[key].astype(np.float64), np.asarray(want[key], np.float64)
         assert g.shape == w.shape, (key, g.shape, w.shape)
         if key in ("S", "beta_eta"):
-            err, tol, unit = np.abs(g - w) / np.abs(w), TOL[key], "rel"
+            err, tol, unit = np.abs(g - w) / np.abs(w), tols[key], "rel"
         else:
-            err, tol, unit = np.abs(g - w), TOL[key] * (umax if key in ("U", "action") else 1.0), "abs"
+            err, tol, unit = np.abs(g - w), tols[key] * (umax if key in ("U", "action") else 1.0), "abs"
         worst = err.max() if np.isfinite(g).all() else np.inf
         cells.append(f"{key} {worst:.1e} ({unit} tol {tol:.1e})")
         if not worst <= tol:
