@@ -503,6 +503,32 @@ int mppi_sim_inverse_dynamics(mppi_ctx_t *ctx, const float *qdd_dev /* [K][n_dof
  * any launch. */
 int mppi_sim_forward_dynamics(mppi_ctx_t *ctx, const float *tau_dev /* [K][n_dof] or NULL */, int terms,
                               float *qdd_dev /* [K][n_dof] */);
+/* How a link ACCELERATES, and what a wrench on a link asks of the joints - the two quantities that stand between the four entries
+ * above and a task-space law (xdd = J qdd + Jdot qd) or an external wrench (tau += J^T w); neither can be had from J, M, tau or the
+ * rigid-body rows.  Conventions of mppi_sim_jacobian: world axes, rows 0-2 linear (the link frame origin), rows 3-5 angular, the
+ * block index is the rigid-body index, bodies of box / sphere actors and links welded to the fixed base have zero Jacobians,
+ * n_dof is the forest's for a fixed-base forest, env-major device tensors.
+ *   acc[k][b] = J_b(q_k) qdd[k]  (left out when qdd_dev is NULL)  + Jdot_b(q_k, qd_k) qd_k  (with MPPI_ID_VELOCITY)
+ * - the time derivative of columns 7:13 of the body's rigid-body row along the motion (qd, qdd), at the envs' current joint
+ * positions and rates: rows 0-2 the classical acceleration of the link frame origin, rows 3-5 the angular acceleration.  A
+ * kinematic quantity: gravity has no part in it, MPPI_ID_GRAVITY or any other bit in terms is MPPI_EINVAL.  terms = 0 with a NULL
+ * qdd_dev writes exact zeros; zero-Jacobian bodies get exact zero rows.  One outward pass of the Newton-Euler recursion on
+ * relative offsets: nothing is a difference of world positions.  qdd_dev and acc_dev must not overlap.
+ *   tau[k] = sum_b J_b(q_k)^T w[k][b],  w = (force on the link, moment about the link frame origin), world axes - the dual of the
+ * Jacobian's rows: the joint forces that do the same work as the wrenches, tau . qd = sum_b w_b . (J_b qd).  To account for the
+ * wrenches ADD them to a tau given to mppi_sim_forward_dynamics, or SUBTRACT them from what mppi_sim_inverse_dynamics returns.  One
+ * inward pass in O(n_dof): no Jacobian is formed.  The wrench rows of zero-Jacobian bodies are IGNORED (by select: a NaN or Inf
+ * there does not reach tau).  wrench_dev and tau_dev must not overlap.
+ * NOT in either, as above: no drives, no limits, no contact forces - the contact-force tensor holds net forces without a point
+ * of application: it is not a wrench, and nothing here reads it.
+ * Launches on the context's stream only - no allocation, no copy, no synchronise: both can sit in a captured graph.
+ * MPPI_EINVAL: a null acc_dev / wrench_dev / tau_dev, a range outside [0, n_rb), unknown bits in terms.  MPPI_EUNSUPPORTED
+ * (mppi_last_error says so): a robot with a MOVING base, a kinematic tree whose launch table lacks the kernel.  Refused before
+ * any launch. */
+int mppi_sim_link_acceleration(mppi_ctx_t *ctx, int rb_first, int rb_count, const float *qdd_dev /* [K][n_dof] or NULL */, int terms,
+                               float *acc_dev /* [K][rb_count][6] */);
+int mppi_sim_wrench_forces(mppi_ctx_t *ctx, int rb_first, int rb_count, const float *wrench_dev /* [K][rb_count][6] */,
+                           float *tau_dev /* [K][n_dof] */);
 int mppi_sim_accumulate_cost(mppi_ctx_t *ctx, int t, const float *cost_dev); /* S += gamma^t c      */
 int mppi_sim_finish(mppi_ctx_t *ctx);                      /* S += control cost                     */
 /* The same horizon in TWO launches for host-side costs that are functions of the state tensors (mppi_isaac.py:57-69 evaluates

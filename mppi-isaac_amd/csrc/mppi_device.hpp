@@ -1519,4 +1519,117 @@ MPPI_HD void forward_dynamics(M &m0, const Pose<T> &P, const V3 *d, const float 
     });
 }
 
+// ---- link accelerations and the joint forces of link wrenches of one env of a FIXED-base robot ----
+// (mppi_sim_link_acceleration / mppi_sim_wrench_forces: the two halves of the Newton-Euler recursion of inverse_dynamics, each
+// on its own - the outward half without the inertias, the inward half without the motion)
+
+// Angular velocity, angular acceleration and the acceleration of the body ORIGIN of every body, world axes
+template <class T>
+struct BodyMotion {
+    V3 w[T::NB ? T::NB : 1], wd[T::NB ? T::NB : 1], ao[T::NB ? T::NB : 1];
+};
+
+// The outward pass of inverse_dynamics without gravity and without the inertias: B of the motion (qd, qdd) at the body poses P.
+// Everything travels from parent to child through the relative offset d[i] only; a revolute joint adds w_parent x (qd a) + qdd a to
+// the angular acceleration, a prismatic one 2 w x (qd a) + qdd a to the origin's.  The accelerations are linear in qdd and
+// quadratic in qd: a part that is not asked for (qdd null, kIdVelocity not in terms) is left out by zeroing its input, so the parts
+// of separate calls are the very sums of one call, and with nothing asked for every product has a zero factor.
+template <class T>
+MPPI_HD void link_accelerations(const Pose<T> &P, const V3 *d, const float *qd, const float *qdd, int terms, BodyMotion<T> &B) {
+    constexpr int NB = T::NB;
+    const bool with_v = (terms & kIdVelocity) != 0;
+    const V3 zero = {0.f, 0.f, 0.f};
+    static_for<0, NB>([&](auto ic) MPPI_LAMBDA {
+        constexpr int i = ic;
+        constexpr int par = T::par[i];
+        constexpr int pj = par < 0 ? 0 : par;
+        const V3 az = {P.R[i].a[2], P.R[i].a[5], P.R[i].a[8]};
+        const bool rev = P.jt[i] == 0;
+        const float vi = with_v ? qd[i] : 0.f, ai = qdd != nullptr ? qdd[i] : 0.f;
+        const V3 wp = par < 0 ? zero : B.w[pj], wdp = par < 0 ? zero : B.wd[pj], ap = par < 0 ? zero : B.ao[pj];
+        const V3 sv = vi * az, sa = ai * az;
+        V3 acc = ap + cross(wdp, d[i]) + cross(wp, cross(wp, d[i]));
+        if (!rev) acc = acc + 2.f * cross(wp, sv) + sa;
+        B.w[i] = rev ? wp + sv : wp;
+        B.wd[i] = rev ? wdp + sa + cross(wp, sv) : wdp;
+        B.ao[i] = acc;
+    });
+}
+
+// a [6] of robot link l from the motion B of the bodies: rows 0-2 the classical acceleration of the link frame origin,
+// a_body + wd x r + w x (w x r) with r = R_body link.p the link's offset on its body, rows 3-5 the angular acceleration - the time
+// derivative of what link_jacobian's J qd reports.  The link's body is a run-time (wave-uniform) index, resolved by a 0/1-weighted
+// blend as in link_pose.  l outside [0, nl) (the body of a box or sphere actor) and links welded to the fixed base: exact zeros.
+template <class T, class M>
+MPPI_HD void link_acceleration(M &m, const Pose<T> &P, const BodyMotion<T> &B, int l, float *a) {
+    const bool robot = l >= 0 && l < m.nl;
+    const int ll = robot ? l : 0;
+    const int body = robot ? m.l[ll].body : -1;
+    M3 Rb;
+    for (int j = 0; j < 9; j++) Rb.a[j] = 0.f;
+    V3 w = {0.f, 0.f, 0.f}, wd = w, ao = w;
+    static_for<0, T::NB>([&](auto ic) MPPI_LAMBDA {
+        constexpr int i = ic;
+        const float s = body == i ? 1.f : 0.f;
+        for (int j = 0; j < 9; j++) Rb.a[j] += s * P.R[i].a[j];
+        w = w + s * B.w[i];
+        wd = wd + s * B.wd[i];
+        ao = ao + s * B.ao[i];
+    });
+    const V3 r = mul(Rb, loadv(m.l[ll].p));
+    const V3 lin = ao + cross(wd, r) + cross(w, cross(w, r));
+    const bool on = body >= 0;
+    a[0] = on ? lin.x : 0.f;
+    a[1] = on ? lin.y : 0.f;
+    a[2] = on ? lin.z : 0.f;
+    a[3] = on ? wd.x : 0.f;
+    a[4] = on ? wd.y : 0.f;
+    a[5] = on ? wd.z : 0.f;
+}
+
+// The wrench (f on the link, n about the link frame origin; world axes) on robot link l, moved to the origin of the link's body and
+// added to that body's sums: F_i += f, N_i += n + r x f, r = R_body link.p.  l outside [0, nl) and links welded to the fixed base
+// take no part - by select, never by a product with zero: a NaN or Inf in such a row does not reach any sum.
+template <class T, class M>
+MPPI_HD void gather_link_wrench(M &m, const Pose<T> &P, int l, V3 f, V3 n, V3 *F, V3 *N) {
+    const bool robot = l >= 0 && l < m.nl;
+    const int ll = robot ? l : 0;
+    const int body = robot ? m.l[ll].body : -1;
+    M3 Rb;
+    for (int j = 0; j < 9; j++) Rb.a[j] = 0.f;
+    static_for<0, T::NB>([&](auto ic) MPPI_LAMBDA {
+        constexpr int i = ic;
+        const float s = body == i ? 1.f : 0.f;
+        for (int j = 0; j < 9; j++) Rb.a[j] += s * P.R[i].a[j];
+    });
+    const V3 r = mul(Rb, loadv(m.l[ll].p));
+    const V3 nb = n + cross(r, f);
+    static_for<0, T::NB>([&](auto ic) MPPI_LAMBDA {
+        constexpr int i = ic;
+        const bool on = body == i;  // (component by component: a select between two V3 objects becomes a select of addresses, and the sums go to scratch)
+        const V3 Fi = F[i] + f, Ni = N[i] + nb;
+        F[i] = {on ? Fi.x : F[i].x, on ? Fi.y : F[i].y, on ? Fi.z : F[i].z};
+        N[i] = {on ? Ni.x : N[i].x, on ? Ni.y : N[i].y, on ? Ni.z : N[i].z};
+    });
+}
+
+// tau [NB] = sum over the links of J_link^T (f, n) from the wrenches gathered on the bodies (F_i, N_i about p_i; gather_link_wrench):
+// the inward pass of inverse_dynamics.  tau_i = a_i . N_i (revolute) or a_i . F_i (prismatic), then the body's sums go to the
+// parent's origin - the same force, its moment moved by d[i] only.  No Jacobian is formed, nothing is a difference of world
+// positions.  F and N are used up.
+template <class T>
+MPPI_HD void wrench_joint_forces(const Pose<T> &P, const V3 *d, V3 *F, V3 *N, float *tau) {
+    static_rfor<0, T::NB>([&](auto ic) MPPI_LAMBDA {
+        constexpr int i = ic;
+        constexpr int par = T::par[i];
+        const V3 az = {P.R[i].a[2], P.R[i].a[5], P.R[i].a[8]};
+        tau[i] = P.jt[i] == 0 ? dot(az, N[i]) : dot(az, F[i]);
+        if constexpr (par >= 0) {
+            constexpr int pj = par < 0 ? 0 : par;
+            N[pj] = N[pj] + N[i] + cross(d[i], F[i]);
+            F[pj] = F[pj] + F[i];
+        }
+    });
+}
+
 }  // namespace mppi

@@ -1400,6 +1400,42 @@ int mppi_sim_forward_dynamics(mppi_ctx_t *c, const float *tau_dev, int terms, fl
     e->sim_forward_dynamics(c, tau_dev, terms, qdd_dev);
     return launch_check();
 }
+namespace {
+int rb_range_check(mppi_ctx *c, const char *what, int rb_first, int rb_count) {
+    if (rb_first < 0 || rb_count < 1 || rb_first >= c->B || rb_count > c->B - rb_first)
+        return fail(MPPI_EINVAL, std::string(what) + ": rigid bodies [" + std::to_string(rb_first) + ", " + std::to_string((long long)rb_first + rb_count) +
+                                     ") outside [0, " + std::to_string(c->B) + ")");
+    return MPPI_OK;
+}
+}  // namespace
+/* the accelerations of links under the motion (qd, qdd), at the envs' current joint positions and rates: launches on the context's
+ * stream, no allocation, no copy, no synchronise (include/mppi_hip.h) */
+int mppi_sim_link_acceleration(mppi_ctx_t *c, int rb_first, int rb_count, const float *qdd_dev, int terms, float *acc_dev) {
+    CTX_TRY(c);
+    if (!acc_dev) return fail(MPPI_EINVAL, "mppi_sim_link_acceleration: null output");
+    if (int rc = rb_range_check(c, "mppi_sim_link_acceleration", rb_first, rb_count)) return rc;
+    if (terms & ~MPPI_ID_VELOCITY)
+        return fail(MPPI_EINVAL, "mppi_sim_link_acceleration: unknown bits in terms = " + std::to_string(terms) +
+                                     " (MPPI_ID_VELOCITY only: gravity has no part in a kinematic quantity)");
+    const TopoEntry *e = nullptr;
+    if (int rc = physics_entry(c, "mppi_sim_link_acceleration", e)) return rc;
+    if (!e->sim_link_acceleration) return fail(MPPI_EUNSUPPORTED, "mppi_sim_link_acceleration: not available for this kinematic tree");
+    e->sim_link_acceleration(c, rb_first, rb_count, qdd_dev, terms, acc_dev);
+    return launch_check();
+}
+/* the joint forces that do the work of wrenches on links, at the envs' current joint positions: one launch on the context's stream,
+ * no allocation, no copy, no synchronise (include/mppi_hip.h) */
+int mppi_sim_wrench_forces(mppi_ctx_t *c, int rb_first, int rb_count, const float *wrench_dev, float *tau_dev) {
+    CTX_TRY(c);
+    if (!wrench_dev) return fail(MPPI_EINVAL, "mppi_sim_wrench_forces: null wrenches");
+    if (!tau_dev) return fail(MPPI_EINVAL, "mppi_sim_wrench_forces: null output");
+    if (int rc = rb_range_check(c, "mppi_sim_wrench_forces", rb_first, rb_count)) return rc;
+    const TopoEntry *e = nullptr;
+    if (int rc = physics_entry(c, "mppi_sim_wrench_forces", e)) return rc;
+    if (!e->sim_wrench_forces) return fail(MPPI_EUNSUPPORTED, "mppi_sim_wrench_forces: not available for this kinematic tree");
+    e->sim_wrench_forces(c, rb_first, rb_count, wrench_dev, tau_dev);
+    return launch_check();
+}
 int mppi_sim_accumulate_cost(mppi_ctx_t *c, int t, const float *cost_dev) {
     CTX_TRY(c);
     if (!cost_dev) return fail(MPPI_EINVAL, "null cost");

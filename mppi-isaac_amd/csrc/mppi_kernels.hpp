@@ -1902,6 +1902,87 @@ __global__ __launch_bounds__(kWave) void k_sim_forward_dynamics(const DevModel *
     __syncthreads();
     store_staged_rows<kLen>(s_row, n_rows, out + (size_t)k0 * kLen, kLen);
 }
+// out [K][rb_count][6] = J qdd (qdd [K][n], null: left out) + Jdot qd (with kIdVelocity) of rigid bodies rb_first .. rb_first + rb_count - 1
+// (link_accelerations / link_acceleration, mppi_device.hpp; zero rows for bodies that are no robot link) at the envs' current joint
+// positions and rates.  The qdd rows come in through the tile at the stride of n floats; the outward pass runs once per env; then
+// the tile is six floats per lane and goes out one body per staging pass, as in k_sim_jacobian.  Every barrier is reached by the
+// whole wavefront (qdd_, rb_count are uniform); rows past K - 1 of the last wavefront are neither loaded nor stored.
+template <class T>
+__global__ __launch_bounds__(kWave) void k_sim_link_acceleration(const DevModel *__restrict__ m, int K, const float *__restrict__ x0_root,
+                                                                 const float *__restrict__ q_, const float *__restrict__ qd_,
+                                                                 const float *__restrict__ base_, const float *__restrict__ qdd_, int terms,
+                                                                 int rb_first, int rb_count, float *__restrict__ out) {
+    constexpr int NB = T::NB, kIn = NB, kInStride = staged_stride(kIn), kLen = 6, kStride = staged_stride(kLen);
+    __shared__ float s_row[kWave * (kInStride > kStride ? kInStride : kStride)];
+    CModel &M = *(CModel *)m;
+    const int k0 = blockIdx.x * kWave, k = k0 + threadIdx.x;
+    const int n_rows = K - k0 < kWave ? K - k0 : kWave;
+    if (qdd_ != nullptr) {
+        load_staged_rows<kIn>(s_row, n_rows, qdd_ + (size_t)k0 * kIn, kIn);
+        __syncthreads();
+    }
+    Pose<T> P;
+    BodyMotion<T> B;
+    if (k < K) {
+        V3 d[NB ? NB : 1];
+        float qd[NB ? NB : 1], qdd[NB ? NB : 1];
+        sim_env_pose<T>(M, K, k, x0_root, q_, base_, P, d);
+        static_for<0, NB>([&](auto ic) {
+            constexpr int i = ic;
+            qd[i] = qd_[(size_t)i * K + k];
+            qdd[i] = qdd_ != nullptr ? s_row[threadIdx.x * kInStride + i] : 0.f;
+        });
+        link_accelerations<T>(P, d, qd, qdd, terms, B);  // (qdd left out: zeros - the same sums, as in k_sim_inverse_dynamics)
+    }
+    __syncthreads();  // the qdd rows are read: the tile changes its stride
+    for (int j = 0; j < rb_count; j++) {
+        if (k < K) link_acceleration<T>(M, P, B, rb_first + j - M.robot_first_rb, s_row + threadIdx.x * kStride);
+        __syncthreads();
+        store_staged_rows<kLen>(s_row, n_rows, out + ((size_t)k0 * rb_count + j) * kLen, (size_t)rb_count * kLen);
+        __syncthreads();
+    }
+}
+// tau [K][n] = sum over rigid bodies rb_first .. rb_first + rb_count - 1 of J_b^T w[k][b] (w [K][rb_count][6]: force on the link, moment
+// about the link frame origin) at the envs' current joint positions (gather_link_wrench / wrench_joint_forces, mppi_device.hpp; the
+// rows of bodies that are no robot link are ignored by select).  rb_count is a run-time number: the wrench rows come in six
+// floats per lane per body through the tile - the loop count is uniform, so the whole wavefront reaches every barrier - and are
+// gathered onto the bodies in registers; one inward pass; tau goes out through the tile at the stride of n floats.
+template <class T>
+__global__ __launch_bounds__(kWave) void k_sim_wrench_forces(const DevModel *__restrict__ m, int K, const float *__restrict__ x0_root,
+                                                             const float *__restrict__ q_, const float *__restrict__ base_, int rb_first, int rb_count,
+                                                             const float *__restrict__ w_, float *__restrict__ out) {
+    constexpr int NB = T::NB, kLen = NB, kStride = staged_stride(kLen), kIn = 6, kInStride = staged_stride(kIn);
+    __shared__ float s_row[kWave * (kInStride > kStride ? kInStride : kStride)];
+    CModel &M = *(CModel *)m;
+    const int k0 = blockIdx.x * kWave, k = k0 + threadIdx.x;
+    const int n_rows = K - k0 < kWave ? K - k0 : kWave;
+    Pose<T> P;
+    V3 d[NB ? NB : 1], F[NB ? NB : 1], N[NB ? NB : 1];
+    if (k < K) sim_env_pose<T>(M, K, k, x0_root, q_, base_, P, d);
+    static_for<0, NB>([&](auto ic) {
+        constexpr int i = ic;
+        F[i] = N[i] = V3{0.f, 0.f, 0.f};
+    });
+    for (int j = 0; j < rb_count; j++) {
+        load_staged_rows<kIn>(s_row, n_rows, w_ + ((size_t)k0 * rb_count + j) * kIn, (size_t)rb_count * kIn);
+        __syncthreads();
+        if (k < K) {
+            const float *w = s_row + threadIdx.x * kInStride;
+            gather_link_wrench<T>(M, P, rb_first + j - M.robot_first_rb, V3{w[0], w[1], w[2]}, V3{w[3], w[4], w[5]}, F, N);
+        }
+        __syncthreads();
+    }
+    if (k < K) {
+        float tau[NB ? NB : 1];
+        wrench_joint_forces<T>(P, d, F, N, tau);
+        static_for<0, NB>([&](auto ic) {
+            constexpr int i = ic;
+            s_row[threadIdx.x * kStride + i] = tau[i];
+        });
+    }
+    __syncthreads();
+    store_staged_rows<kLen>(s_row, n_rows, out + (size_t)k0 * kLen, kLen);
+}
 
 // Parity / debug entry (mppi_eval_cost): the cost program of the context evaluated by the interpreter the rollout kernels run
 // (program_cost_with, mppi_device.hpp) on CALLER-GIVEN simulator answers - reference-layout rows of n envs - instead of the
@@ -2096,6 +2177,8 @@ struct TopoEntry {
     void (*sim_mass_matrix)(mppi_ctx *, float *);         // mppi_sim_mass_matrix
     void (*sim_inverse_dynamics)(mppi_ctx *, const float *, int, float *);  // mppi_sim_inverse_dynamics
     void (*sim_forward_dynamics)(mppi_ctx *, const float *, int, float *);  // mppi_sim_forward_dynamics
+    void (*sim_link_acceleration)(mppi_ctx *, int, int, const float *, int, float *);  // mppi_sim_link_acceleration
+    void (*sim_wrench_forces)(mppi_ctx *, int, int, const float *, float *);            // mppi_sim_wrench_forces
     hipError_t (*raise_lds)(size_t, size_t);
     size_t (*static_lds)();  // largest static __shared__ footprint among the contact-scene kernels (counts against the 160 KiB too)
 };
@@ -2288,6 +2371,16 @@ void launch_sim_forward_dynamics_t(mppi_ctx *c, const float *tau, int terms, flo
                        c->scene ? c->d_base : nullptr, tau, terms, out);
 }
 template <class T>
+void launch_sim_link_acceleration_t(mppi_ctx *c, int rb_first, int rb_count, const float *qdd, int terms, float *out) {
+    hipLaunchKernelGGL(k_sim_link_acceleration<T>, dim3(c->n_waves), dim3(kWave), 0, c->stream, c->d_model, c->K, c->d_x0_root, c->d_q, c->d_qd,
+                       c->scene ? c->d_base : nullptr, qdd, terms, rb_first, rb_count, out);
+}
+template <class T>
+void launch_sim_wrench_forces_t(mppi_ctx *c, int rb_first, int rb_count, const float *w, float *out) {
+    hipLaunchKernelGGL(k_sim_wrench_forces<T>, dim3(c->n_waves), dim3(kWave), 0, c->stream, c->d_model, c->K, c->d_x0_root, c->d_q,
+                       c->scene ? c->d_base : nullptr, rb_first, rb_count, w, out);
+}
+template <class T>
 void launch_rollout_t(mppi_ctx *c) { launch_rollout_kernel(k_rollout<T>, c->n_waves, kWave, 0, c); }
 template <class T>
 void launch_sim_step_t(mppi_ctx *c, int mode, int t, const float *u_ext) {
@@ -2326,11 +2419,13 @@ void fill_topo_entry_free(TopoEntry &e) {
     e.materialise = &launch_materialise_t<T>;
     e.combine_world = &launch_combine_world_t<T>;
     e.eval_cost = &launch_eval_cost_t<T>;
-    if constexpr (T::NBASE == 1) {  // (forests of several moving bases are refused by all four entries: nothing to launch)
+    if constexpr (T::NBASE == 1) {  // (forests of several moving bases are refused by all six entries: nothing to launch)
         e.sim_jacobian = &launch_sim_jacobian_t<T>;
         e.sim_mass_matrix = &launch_sim_mass_matrix_t<T>;
         e.sim_inverse_dynamics = &launch_sim_inverse_dynamics_t<T>;
         e.sim_forward_dynamics = &launch_sim_forward_dynamics_t<T>;
+        e.sim_link_acceleration = &launch_sim_link_acceleration_t<T>;
+        e.sim_wrench_forces = &launch_sim_wrench_forces_t<T>;
     }
 }
 template <class T>

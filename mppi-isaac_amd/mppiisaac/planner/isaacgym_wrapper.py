@@ -649,6 +649,7 @@ class IsaacGymWrapper:
         self._jacobians, self._mass_matrix = {}, None   # acquire_jacobian_tensor / acquire_mass_matrix_tensor: filled by refresh_*()
         self._bias_force = None                         # acquire_bias_force_tensor: filled by refresh_bias_force_tensors()
         self._free_acceleration = None                  # acquire_free_acceleration_tensor: filled by refresh_free_acceleration_tensors()
+        self._link_bias_acceleration = {}               # acquire_link_bias_acceleration_tensor: filled by refresh_link_bias_acceleration_tensors()
         self._visualize_link_present = sc.viz_link_index() >= 0
         self.visualize_link_buffer = []
         if self._visualize_link_present:
@@ -1113,6 +1114,82 @@ class IsaacGymWrapper:
             self._physics_call(self._lib.mppi_sim_forward_dynamics, _dev_ptr(units[i]), 0, _dev_ptr(cols[i]), what=self._FD_WHAT)
         low = torch.tril(cols.permute(1, 2, 0))      # [K, row, column]
         return low + torch.tril(low, -1).transpose(1, 2)
+
+    # ------------------------------------------------------------------ link accelerations and the joint forces of link wrenches
+    # What a task-space law needs beside J and qdd: xdd = J qdd + Jdot qd of a link (mppi_sim_link_acceleration), and tau = J^T w of
+    # wrenches on links (mppi_sim_wrench_forces) without forming a Jacobian.  Conventions of the Jacobians: world axes, rows 0-2 the
+    # link frame origin (linear), 3-5 angular, the link index is the rigid-body index within the actor; w = (force on the link,
+    # moment about the link frame origin).  Fixed-base robots and fixed-base forests.
+    _LA_WHAT = "link accelerations and wrench forces"
+
+    def _qdd_rows(self, qdd):
+        K, n = self.num_envs, self.scene.n_dof
+        if qdd is None:
+            return None
+        qdd = torch.as_tensor(qdd, dtype=torch.float32, device=self.device)
+        if tuple(qdd.shape) == (n,):
+            qdd = qdd.expand(K, n)
+        elif tuple(qdd.shape) != (K, n):
+            raise ValueError(f"qdd has shape {tuple(qdd.shape)}: expected [{n}] or [{K}, {n}]")
+        return qdd.contiguous()
+
+    def _link_acceleration_call(self, first, count, qdd, velocity):
+        self._live_envs_only(self._LA_WHAT)
+        qdd = self._qdd_rows(qdd)
+        out = torch.empty((self.num_envs, count, 6), dtype=torch.float32, device=self.device)
+        self._physics_call(self._lib.mppi_sim_link_acceleration, first, count, _dev_ptr(qdd), capi.ID_VELOCITY if velocity else 0, _dev_ptr(out),
+                           what=self._LA_WHAT)
+        return out
+
+    def link_accelerations(self, actor_name: str, qdd=None, velocity=True):
+        """a fresh [K, L, 6] tensor J qdd (qdd None: left out) + Jdot qd (velocity) of every rigid body of the actor at the envs'
+        current joint positions and rates.  qdd: [n_dof], the same acceleration for every env, or [K, n_dof]."""
+        return self._link_acceleration_call(*self._actor_rb_range(actor_name), qdd, velocity)
+
+    def get_actor_link_acceleration_by_name(self, actor_name: str, link_name: str, qdd=None, velocity=True):
+        """a fresh [K, 6] acceleration of one link (a one-body launch): the counterpart of get_actor_link_jacobian_by_name"""
+        rb = self.scene.rigid_body_index(actor_name, link_name)
+        return self._link_acceleration_call(rb, 1, qdd, velocity)[:, 0, :]
+
+    def acquire_link_bias_acceleration_tensor(self, actor_name: str):
+        """[K, L, 6]: Jdot qd of every rigid body of the actor - the velocity-product acceleration of the task-space equation
+        xdd = J qdd + Jdot qd.  Zero until refresh_link_bias_acceleration_tensors()."""
+        self._live_envs_only(self._LA_WHAT)
+        if actor_name not in self._link_bias_acceleration:
+            first, count = self._actor_rb_range(actor_name)
+            t = torch.zeros((self.num_envs, count, 6), dtype=torch.float32, device=self.device)
+            self._link_bias_acceleration[actor_name] = (first, count, t)
+        return self._link_bias_acceleration[actor_name][2]
+
+    def refresh_link_bias_acceleration_tensors(self) -> None:
+        self._live_envs_only(self._LA_WHAT)
+        for first, count, t in self._link_bias_acceleration.values():
+            self._physics_call(self._lib.mppi_sim_link_acceleration, first, count, None, capi.ID_VELOCITY, _dev_ptr(t), what=self._LA_WHAT)
+
+    def _wrench_forces_call(self, first, count, wrenches, one, many):
+        self._live_envs_only(self._LA_WHAT)
+        K = self.num_envs
+        w = torch.as_tensor(wrenches, dtype=torch.float32, device=self.device)
+        if tuple(w.shape) == one:
+            w = w.expand(K, *one)
+        elif tuple(w.shape) != many:
+            raise ValueError(f"wrenches have shape {tuple(w.shape)}: expected {list(one)} or {list(many)}")
+        w = w.contiguous()
+        out = torch.empty((K, self.scene.n_dof), dtype=torch.float32, device=self.device)
+        self._physics_call(self._lib.mppi_sim_wrench_forces, first, count, _dev_ptr(w), _dev_ptr(out), what=self._LA_WHAT)
+        return out
+
+    def joint_forces_from_wrenches(self, actor_name: str, wrenches):
+        """a fresh [K, n_dof] tensor sum_b J_b^T w_b: the joint forces that do the work of the wrenches on the actor's rigid bodies
+        (ADD them to a tau given to forward_dynamics, SUBTRACT them from what inverse_dynamics returns).  wrenches: [L, 6], the
+        same for every env, or [K, L, 6]; the rows of bodies without a Jacobian are ignored."""
+        first, count = self._actor_rb_range(actor_name)
+        return self._wrench_forces_call(first, count, wrenches, (count, 6), (self.num_envs, count, 6))
+
+    def joint_forces_from_link_wrench(self, actor_name: str, link_name: str, wrench):
+        """a fresh [K, n_dof] tensor J_link^T w of one wrench on one link (a one-body launch).  wrench: [6] or [K, 6]."""
+        rb = self.scene.rigid_body_index(actor_name, link_name)
+        return self._wrench_forces_call(rb, 1, wrench, (6,), (self.num_envs, 6))
 
     # ------------------------------------------------------------------ env mutation (reference :423-427, :695-758)
     def _restart(self):
