@@ -529,6 +529,28 @@ int mppi_sim_link_acceleration(mppi_ctx_t *ctx, int rb_first, int rb_count, cons
                                float *acc_dev /* [K][rb_count][6] */);
 int mppi_sim_wrench_forces(mppi_ctx_t *ctx, int rb_first, int rb_count, const float *wrench_dev /* [K][rb_count][6] */,
                            float *tau_dev /* [K][n_dof] */);
+/* J and M of a robot with a MOVING base (boxer, a jackal, albert, anymal: what the six entries above refuse), with the six base
+ * columns gym's tensors carry for a floating-base actor.  Generalised velocity v = (root linvel, root angvel, qd): columns 0-2
+ * are columns 7:10 of the robot's root row (the velocity of the root link frame origin, world axes), columns 3-5 are columns
+ * 10:13 of it (angular velocity, world axes), columns 6.. the joints in DOF order.
+ *   J_b v = columns 7:13 of body b's rigid-body row as mppi_sim_materialise reports it - the row convention of mppi_sim_jacobian
+ * (rows 0-2 linear of the link frame origin, rows 3-5 angular; the block index is the rigid-body index).  The base columns are
+ * [[1, -[r]x], [0, 1]] with r = p_link - p_base, formed from the relative offsets along the path and never as a difference of
+ * world positions; links welded to the base have that block and no joint column; bodies of box / sphere actors get exact zero
+ * blocks.
+ *   M = the inertia of the packed model in these coordinates, T = v^T M v / 2; no drive terms; symmetric bit for bit (both
+ * triangles are written from one value).  Base block [[m 1, -[h]x], [[h]x, I]] of the whole robot's composite inertia about the
+ * base origin (base_mass / base_h / base_Io included); the column of joint i couples it to the base by the spatial force (f, n)
+ * of a unit joint acceleration on the composite body below the joint, its moment taken about the base origin.
+ * Each env reads ITS OWN base pose (mppi_sim_set_states, the steps); neither result depends on where the base stands.
+ * Launches on the context's stream only - no allocation, no copy, no synchronise: both can sit in a captured graph.
+ * MPPI_EINVAL: a null output, a range outside [0, n_rb).  MPPI_EUNSUPPORTED (mppi_last_error says which): a fixed-base robot or
+ * fixed-base forest (use mppi_sim_jacobian / mppi_sim_mass_matrix), a forest of several moving bases (n_extra_bases > 0), a
+ * kinematic tree whose launch table lacks the kernel.  Refused before any launch.
+ * STILL refused for a moving base: mppi_sim_inverse_dynamics, mppi_sim_forward_dynamics, mppi_sim_link_acceleration and
+ * mppi_sim_wrench_forces (they need the bias force of a moving base), and mppi_sim_jacobian / mppi_sim_mass_matrix themselves. */
+int mppi_sim_floating_jacobian(mppi_ctx_t *ctx, int rb_first, int rb_count, float *jac_dev /* [K][rb_count][6][6 + n_dof] */);
+int mppi_sim_floating_mass_matrix(mppi_ctx_t *ctx, float *M_dev /* [K][6 + n_dof][6 + n_dof] */);
 int mppi_sim_accumulate_cost(mppi_ctx_t *ctx, int t, const float *cost_dev); /* S += gamma^t c      */
 int mppi_sim_finish(mppi_ctx_t *ctx);                      /* S += control cost                     */
 /* The same horizon in TWO launches for host-side costs that are functions of the state tensors (mppi_isaac.py:57-69 evaluates

@@ -1123,7 +1123,8 @@ MPPI_HD void rigid_body_link(CModel &m, const float *root, const float *q, const
     o[10] = vb.a.x; o[11] = vb.a.y; o[12] = vb.a.z;
 }
 
-// ---- link Jacobians and joint-space mass matrix of one env of a FIXED-base robot (mppi_sim_jacobian / mppi_sim_mass_matrix) ----
+// ---- link Jacobians and joint-space mass matrix of one env: of a FIXED-base robot (mppi_sim_jacobian / mppi_sim_mass_matrix) and,
+// ---- with six base columns in front of the joints, of a robot with ONE moving base (mppi_sim_floating_jacobian / _mass_matrix) ----
 // bodies on the path from the base to body i, body i included, as a bit mask: a compile-time fact of the tree
 template <class T>
 constexpr unsigned ancestor_mask(int i) {
@@ -1187,15 +1188,27 @@ MPPI_HD void forward_kinematics_offsets(M &m0, const float *q, Pose<T> &P, V3 *d
 // prismatic one, zero for every other joint.  The lever arm p_link - p_i is the sum of the offsets along the path (body_offsets),
 // collected on the way from the link's body to the base.  l outside [0, nl) (the body of a box or sphere actor) and links
 // welded to the fixed base give a zero block.
-template <class T, class M>
-MPPI_HD void link_jacobian(M &m, const Pose<T> &P, const V3 *d, int l, float *J) {
-    constexpr int NB = T::NB;
+//
+// MOVING = true (floating_link_jacobian): J [6][6 + NB] in the generalised velocity v = (root linvel, root angvel, qd) - the
+// velocity of the root link frame origin and the angular velocity, world axes, columns 7:13 of the robot's root row.  The joint
+// columns stand at 6 + i and are the very values of the fixed routine; the walk up the path ends at the base origin, where the
+// lever arm is r = p_link - p_base - a sum of relative offsets, never a difference of world positions - and the base columns are
+// [[1, -[r]x], [0, 1]].  Links welded to the base have r = R_base p_link and no joint column; bodies that are no robot link
+// still get a zero block, base columns included.
+template <bool MOVING, class T, class M>
+MPPI_HD void link_jacobian_columns(M &m, const Pose<T> &P, const V3 *d, int l, float *J) {
+    constexpr int NB = T::NB, C0 = MOVING ? 6 : 0, LD = C0 + NB;
     const bool robot = l >= 0 && l < m.nl;
     const int ll = robot ? l : 0;
     const int body = robot ? m.l[ll].body : -1;
     unsigned anc = 0;
     M3 Rb;  // rotation of the link's body: a 0/1-weighted blend, as link_pose
-    for (int j = 0; j < 9; j++) Rb.a[j] = 0.f;
+    if constexpr (MOVING) {
+        const float wb = robot && body < 0 ? 1.f : 0.f;
+        for (int j = 0; j < 9; j++) Rb.a[j] = wb * P.Rb.a[j];
+    } else {
+        for (int j = 0; j < 9; j++) Rb.a[j] = 0.f;
+    }
     static_for<0, NB>([&](auto ic) MPPI_LAMBDA {
         constexpr int i = ic;
         anc = body == i ? ancestor_mask<T>(i) : anc;
@@ -1208,14 +1221,48 @@ MPPI_HD void link_jacobian(M &m, const Pose<T> &P, const V3 *d, int l, float *J)
         const bool on = ((anc >> i) & 1u) != 0, rev = P.jt[i] == 0;
         const V3 az = {P.R[i].a[2], P.R[i].a[5], P.R[i].a[8]};
         const V3 lin = rev ? cross(az, arm) : az;
-        J[0 * NB + i] = on ? lin.x : 0.f;
-        J[1 * NB + i] = on ? lin.y : 0.f;
-        J[2 * NB + i] = on ? lin.z : 0.f;
-        J[3 * NB + i] = on && rev ? az.x : 0.f;
-        J[4 * NB + i] = on && rev ? az.y : 0.f;
-        J[5 * NB + i] = on && rev ? az.z : 0.f;
+        J[0 * LD + C0 + i] = on ? lin.x : 0.f;
+        J[1 * LD + C0 + i] = on ? lin.y : 0.f;
+        J[2 * LD + C0 + i] = on ? lin.z : 0.f;
+        J[3 * LD + C0 + i] = on && rev ? az.x : 0.f;
+        J[4 * LD + C0 + i] = on && rev ? az.y : 0.f;
+        J[5 * LD + C0 + i] = on && rev ? az.z : 0.f;
         if (on) arm = arm + d[i];
     });
+    if constexpr (MOVING) {  // arm = r = p_link - p_base
+        const float one = robot ? 1.f : 0.f;
+        const V3 zero = {0.f, 0.f, 0.f};
+        const V3 r = robot ? arm : zero, n = robot ? -1.f * arm : zero;  // (by select: a body that is no robot link gets +0 everywhere)
+        const float B[6][6] = {{one, 0.f, 0.f, 0.f, r.z, n.y}, {0.f, one, 0.f, n.z, 0.f, r.x}, {0.f, 0.f, one, r.y, n.x, 0.f},
+                               {0.f, 0.f, 0.f, one, 0.f, 0.f},  {0.f, 0.f, 0.f, 0.f, one, 0.f},  {0.f, 0.f, 0.f, 0.f, 0.f, one}};
+        for (int a = 0; a < 6; a++)
+            for (int c = 0; c < 6; c++) J[a * LD + c] = B[a][c];
+    }
+}
+template <class T, class M>
+MPPI_HD void link_jacobian(M &m, const Pose<T> &P, const V3 *d, int l, float *J) { link_jacobian_columns<false, T>(m, P, d, l, J); }
+template <class T, class M>
+MPPI_HD void floating_link_jacobian(M &m, const Pose<T> &P, const V3 *d, int l, float *J) { link_jacobian_columns<true, T>(m, P, d, l, J); }
+
+// a rigid body's first moment and rotational inertia about ITS OWN origin in world axes, from the body-axes first moment hb = m com
+// and the inertia about the centre of mass Ic (xx xy xz yy yz zz):  h = R hb,  I = R Ic R^T + m (|c|^2 1 - c c^T),  c = h / m
+MPPI_HD void rigid_inertia_about_origin(const M3 &R, const float *hb, const float *Ic, float invm, V3 &h, S3 &I) {
+    h = mul(R, V3{hb[0], hb[1], hb[2]});
+    float T9[9];  // R * Ic
+    for (int r = 0; r < 3; r++) {
+        const float r0 = R.a[3 * r], r1 = R.a[3 * r + 1], r2 = R.a[3 * r + 2];
+        T9[3 * r + 0] = r0 * Ic[0] + r1 * Ic[1] + r2 * Ic[2];
+        T9[3 * r + 1] = r0 * Ic[1] + r1 * Ic[3] + r2 * Ic[4];
+        T9[3 * r + 2] = r0 * Ic[2] + r1 * Ic[4] + r2 * Ic[5];
+    }
+    const V3 c = invm * h;
+    const float hh = dot(h, c);
+    I.xx = T9[0] * R.a[0] + T9[1] * R.a[1] + T9[2] * R.a[2] + hh - h.x * c.x;
+    I.xy = T9[0] * R.a[3] + T9[1] * R.a[4] + T9[2] * R.a[5] - h.x * c.y;
+    I.xz = T9[0] * R.a[6] + T9[1] * R.a[7] + T9[2] * R.a[8] - h.x * c.z;
+    I.yy = T9[3] * R.a[3] + T9[4] * R.a[4] + T9[5] * R.a[5] + hh - h.y * c.y;
+    I.yz = T9[3] * R.a[6] + T9[4] * R.a[7] + T9[5] * R.a[8] - h.y * c.z;
+    I.zz = T9[6] * R.a[6] + T9[7] * R.a[7] + T9[8] * R.a[8] + hh - h.z * c.z;
 }
 
 // M [NB][NB] (row-major) at the body poses P: the composite-rigid-body inertia of the packed model, no drive terms.
@@ -1223,36 +1270,39 @@ MPPI_HD void link_jacobian(M &m, const Pose<T> &P, const V3 *d, int l, float *J)
 // world axes and moved to the parent by the relative offset d[i] = p_i - p_parent only: about the world origin a wrist joint's
 // S^T I S of 1e-3 kg m^2 would be what is left of terms m |c|^2 of order 1, and less the further the base stands from the origin
 // ("One row found something").  Both triangles are written from the same value.
-template <class T, class M>
-MPPI_HD void mass_matrix(M &m0, const Pose<T> &P, const V3 *d, float *Mo) {
-    constexpr int NB = T::NB;
+//
+// MOVING = true (floating_mass_matrix): M [6 + NB][6 + NB] in the generalised velocity v = (root linvel, root angvel, qd) of
+// floating_link_jacobian, T = v^T M v / 2.  The joint block stands at [6:, 6:] and is the very sum of the fixed routine.  The
+// bodies next to the base hand their composite inertia on to the BASE origin by the same rule, where it joins the base's own
+// (base_m, base_hb, base_Ic): the base block is [[m 1, -[h]x], [[h]x, I]] of that sum.  The coupling column of joint i is the
+// spatial force (f, n) the sweep already carries up the path, its moment moved one more offset, to the base origin: rows 0-2
+// are f, rows 3-5 are n.
+template <bool MOVING, class T, class M>
+MPPI_HD void mass_matrix_blocks(M &m0, const Pose<T> &P, const V3 *d, float *Mo) {
+    constexpr int NB = T::NB, C0 = MOVING ? 6 : 0, LD = C0 + NB;
     M *mp = &m0;
     float cm[NB ? NB : 1];
     V3 ch[NB ? NB : 1];
     S3 cI[NB ? NB : 1];
+    float bm = 0.f;  // MOVING: the whole robot about the base origin
+    V3 bh = {0.f, 0.f, 0.f};
+    S3 bI = {};
+    if constexpr (MOVING) {
+        bm = m0.base_m;
+        const float hb3[3] = {m0.base_hb[0], m0.base_hb[1], m0.base_hb[2]};
+        const float Ic6[6] = {m0.base_Ic[0], m0.base_Ic[1], m0.base_Ic[2], m0.base_Ic[3], m0.base_Ic[4], m0.base_Ic[5]};
+        rigid_inertia_about_origin(P.Rb, hb3, Ic6, bm > 0.f ? 1.f / bm : 0.f, bh, bI);
+    }
     static_rfor<0, NB>([&](auto ic) MPPI_LAMBDA {
         constexpr int i = ic;
         constexpr int par = T::par[i];
         const BodyK1 b = load_block<BodyK1>(launder(mp)->b[i].k1);  // (fetched where it is used, as in body_offsets)
         const M3 &R = P.R[i];
-        // the body's own inertia about p_i: I = R Ic R^T + m (|c|^2 1 - c c^T), h = m c, c = R com
-        const V3 h = mul(R, V3{b.hb(0), b.hb(1), b.hb(2)});
-        float T9[9];  // R * Ic
-        for (int r = 0; r < 3; r++) {
-            const float r0 = R.a[3 * r], r1 = R.a[3 * r + 1], r2 = R.a[3 * r + 2];
-            T9[3 * r + 0] = r0 * b.Ic(0) + r1 * b.Ic(1) + r2 * b.Ic(2);
-            T9[3 * r + 1] = r0 * b.Ic(1) + r1 * b.Ic(3) + r2 * b.Ic(4);
-            T9[3 * r + 2] = r0 * b.Ic(2) + r1 * b.Ic(4) + r2 * b.Ic(5);
-        }
-        const V3 c = b.invm * h;
-        const float hh = dot(h, c);
+        // the body's own inertia about p_i
+        const float hb3[3] = {b.hb(0), b.hb(1), b.hb(2)}, Ic6[6] = {b.Ic(0), b.Ic(1), b.Ic(2), b.Ic(3), b.Ic(4), b.Ic(5)};
+        V3 h;
         S3 I;
-        I.xx = T9[0] * R.a[0] + T9[1] * R.a[1] + T9[2] * R.a[2] + hh - h.x * c.x;
-        I.xy = T9[0] * R.a[3] + T9[1] * R.a[4] + T9[2] * R.a[5] - h.x * c.y;
-        I.xz = T9[0] * R.a[6] + T9[1] * R.a[7] + T9[2] * R.a[8] - h.x * c.z;
-        I.yy = T9[3] * R.a[3] + T9[4] * R.a[4] + T9[5] * R.a[5] + hh - h.y * c.y;
-        I.yz = T9[3] * R.a[6] + T9[4] * R.a[7] + T9[5] * R.a[8] - h.y * c.z;
-        I.zz = T9[6] * R.a[6] + T9[7] * R.a[7] + T9[8] * R.a[8] + hh - h.z * c.z;
+        rigid_inertia_about_origin(R, hb3, Ic6, b.invm, h, I);
         float mc = b.m;
         V3 hc = h;
         if constexpr (last_child<T>(i) >= 0) {  // the subtrees below, already about p_i
@@ -1265,7 +1315,7 @@ MPPI_HD void mass_matrix(M &m0, const Pose<T> &P, const V3 *d, float *Mo) {
         const bool rev = P.jt[i] == 0;
         const V3 f = rev ? cross(az, hc) : mc * az;
         V3 n = rev ? mul(I, az) : cross(hc, az);
-        Mo[i * NB + i] = rev ? dot(az, n) : mc;
+        Mo[(C0 + i) * LD + C0 + i] = rev ? dot(az, n) : mc;
         V3 up = d[i];  // from the origin the moment is taken about to the next body on the way to the base
         static_rfor<0, i>([&](auto jc) MPPI_LAMBDA {
             constexpr int j = jc;
@@ -1276,10 +1326,18 @@ MPPI_HD void mass_matrix(M &m0, const Pose<T> &P, const V3 *d, float *Mo) {
                 const V3 aj = {P.R[j].a[2], P.R[j].a[5], P.R[j].a[8]};
                 v = P.jt[j] == 0 ? dot(aj, n) : dot(aj, f);
             }
-            Mo[i * NB + j] = v;
-            Mo[j * NB + i] = v;
+            Mo[(C0 + i) * LD + C0 + j] = v;
+            Mo[(C0 + j) * LD + C0 + i] = v;
         });
-        if constexpr (par >= 0) {
+        if constexpr (MOVING) {
+            n = n + cross(up, f);  // ... and about the base origin
+            const float col[6] = {f.x, f.y, f.z, n.x, n.y, n.z};
+            for (int a = 0; a < 6; a++) {
+                Mo[a * LD + C0 + i] = col[a];
+                Mo[(C0 + i) * LD + a] = col[a];
+            }
+        }
+        if constexpr (par >= 0 || MOVING) {
             // to the parent's origin: h' = h + m d, I' = I + 2 (e.d) 1 - (e d^T + d e^T) with e = h + m d / 2
             constexpr int pj = par < 0 ? 0 : par;
             const V3 dd = d[i];
@@ -1293,7 +1351,11 @@ MPPI_HD void mass_matrix(M &m0, const Pose<T> &P, const V3 *d, float *Mo) {
             Ip.xz = I.xz - (e.x * dd.z + dd.x * e.z);
             Ip.yz = I.yz - (e.y * dd.z + dd.y * e.z);
             const V3 hp = hc + mc * dd;
-            if constexpr (last_child<T>(pj) == i) {
+            if constexpr (par < 0) {  // (MOVING) next to the base: joins the base's own inertia
+                bm += mc;
+                bh = bh + hp;
+                bI.xx += Ip.xx; bI.xy += Ip.xy; bI.xz += Ip.xz; bI.yy += Ip.yy; bI.yz += Ip.yz; bI.zz += Ip.zz;
+            } else if constexpr (last_child<T>(pj) == i) {
                 cm[pj] = mc;
                 ch[pj] = hp;
                 cI[pj] = Ip;
@@ -1304,7 +1366,18 @@ MPPI_HD void mass_matrix(M &m0, const Pose<T> &P, const V3 *d, float *Mo) {
             }
         }
     });
+    if constexpr (MOVING) {
+        const float nx = -bh.x, ny = -bh.y, nz = -bh.z;
+        const float B[6][6] = {{bm, 0.f, 0.f, 0.f, bh.z, ny},      {0.f, bm, 0.f, nz, 0.f, bh.x},      {0.f, 0.f, bm, bh.y, nx, 0.f},
+                               {0.f, nz, bh.y, bI.xx, bI.xy, bI.xz}, {bh.z, 0.f, nx, bI.xy, bI.yy, bI.yz}, {ny, bh.x, 0.f, bI.xz, bI.yz, bI.zz}};
+        for (int a = 0; a < 6; a++)
+            for (int c = 0; c < 6; c++) Mo[a * LD + c] = B[a][c];
+    }
 }
+template <class T, class M>
+MPPI_HD void mass_matrix(M &m0, const Pose<T> &P, const V3 *d, float *Mo) { mass_matrix_blocks<false, T>(m0, P, d, Mo); }
+template <class T, class M>
+MPPI_HD void floating_mass_matrix(M &m0, const Pose<T> &P, const V3 *d, float *Mo) { mass_matrix_blocks<true, T>(m0, P, d, Mo); }
 
 // ---- inverse dynamics of one env of a FIXED-base robot (mppi_sim_inverse_dynamics) ----
 enum { kIdGravity = 1, kIdVelocity = 2 };  // MPPI_ID_GRAVITY / MPPI_ID_VELOCITY (include/mppi_hip.h)

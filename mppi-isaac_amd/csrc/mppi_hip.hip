@@ -1436,6 +1436,44 @@ int mppi_sim_wrench_forces(mppi_ctx_t *c, int rb_first, int rb_count, const floa
     e->sim_wrench_forces(c, rb_first, rb_count, wrench_dev, tau_dev);
     return launch_check();
 }
+namespace {
+// the launch-table row of a context with ONE moving base, for the two entries that compute the six base columns; everything
+// else is refused before any launch, each case with a text of its own
+int floating_entry(mppi_ctx *c, const char *what, const char *fixed_entry, const TopoEntry *&e) {
+    if (c->hm.n_bases > 1)
+        return fail(MPPI_EUNSUPPORTED, std::string(what) + ": unsupported for a forest of several moving bases (" + std::to_string(c->hm.n_bases) +
+                                       " bases: one block of six base columns per robot is not computed); one moving-base robot per env only");
+    if (!c->hm.floating)
+        return fail(MPPI_EUNSUPPORTED, std::string(what) + ": this robot has a fixed base (there are no base columns); use " + fixed_entry +
+                                       " for fixed-base robots and fixed-base forests");
+    int parents[MPPI_MAX_BODIES];
+    for (int i = 0; i < c->hm.nb; i++) parents[i] = c->hm.b[i].k0.parent;
+    e = find_entry(c->hm.nb, parents, c->scene, c->hm.n_free);
+    if (!e) return fail(MPPI_EUNSUPPORTED, std::string(what) + ": not available for this kinematic tree");
+    return MPPI_OK;
+}
+}  // namespace
+/* J and M of a robot with a moving base, in the generalised velocity (root linvel, root angvel, qd): launches on the context's
+ * stream, no allocation, no copy, no synchronise (include/mppi_hip.h) */
+int mppi_sim_floating_jacobian(mppi_ctx_t *c, int rb_first, int rb_count, float *jac_dev) {
+    CTX_TRY(c);
+    if (!jac_dev) return fail(MPPI_EINVAL, "mppi_sim_floating_jacobian: null output");
+    if (int rc = rb_range_check(c, "mppi_sim_floating_jacobian", rb_first, rb_count)) return rc;
+    const TopoEntry *e = nullptr;
+    if (int rc = floating_entry(c, "mppi_sim_floating_jacobian", "mppi_sim_jacobian", e)) return rc;
+    if (!e->sim_floating_jacobian) return fail(MPPI_EUNSUPPORTED, "mppi_sim_floating_jacobian: not available for this kinematic tree");
+    e->sim_floating_jacobian(c, rb_first, rb_count, jac_dev);
+    return launch_check();
+}
+int mppi_sim_floating_mass_matrix(mppi_ctx_t *c, float *M_dev) {
+    CTX_TRY(c);
+    if (!M_dev) return fail(MPPI_EINVAL, "mppi_sim_floating_mass_matrix: null output");
+    const TopoEntry *e = nullptr;
+    if (int rc = floating_entry(c, "mppi_sim_floating_mass_matrix", "mppi_sim_mass_matrix", e)) return rc;
+    if (!e->sim_floating_mass_matrix) return fail(MPPI_EUNSUPPORTED, "mppi_sim_floating_mass_matrix: not available for this kinematic tree");
+    e->sim_floating_mass_matrix(c, M_dev);
+    return launch_check();
+}
 int mppi_sim_accumulate_cost(mppi_ctx_t *c, int t, const float *cost_dev) {
     CTX_TRY(c);
     if (!cost_dev) return fail(MPPI_EINVAL, "null cost");

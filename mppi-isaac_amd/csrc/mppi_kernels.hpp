@@ -1983,6 +1983,51 @@ __global__ __launch_bounds__(kWave) void k_sim_wrench_forces(const DevModel *__r
     __syncthreads();
     store_staged_rows<kLen>(s_row, n_rows, out + (size_t)k0 * kLen, kLen);
 }
+// ---- the same two tensors for a robot with a MOVING base (mppi_sim_floating_jacobian / mppi_sim_floating_mass_matrix) ----
+// Generalised velocity (root linvel, root angvel, qd): six base columns in front of the joints.  Every env reads ITS OWN base
+// pose - the rows k_materialise_scene reads (base_: a moving base is always a contact-scene context); only the orientation and
+// the relative offsets enter, so the x/y-relative coordinates of those rows need no undoing.
+// out [K][rb_count][6][6 + n]: floating_link_jacobian of rigid bodies rb_first .. rb_first + rb_count - 1, staged as k_sim_jacobian
+template <class T>
+__global__ __launch_bounds__(kWave) void k_sim_floating_jacobian(const DevModel *__restrict__ m, int K, const float *__restrict__ x0_root,
+                                                                 const float *__restrict__ q_, const float *__restrict__ base_, int rb_first,
+                                                                 int rb_count, float *__restrict__ out) {
+    constexpr int kLen = 6 * (6 + T::NB), kStride = staged_stride(kLen);
+    __shared__ float s_row[kWave * kStride];
+    CModel &M = *(CModel *)m;
+    const int k0 = blockIdx.x * kWave, k = k0 + threadIdx.x;
+    const int n_rows = K - k0 < kWave ? K - k0 : kWave;
+    Pose<T> P;
+    V3 d[T::NB ? T::NB : 1];
+    if (k < K) sim_env_pose<T>(M, K, k, x0_root, q_, base_, P, d);
+    for (int j = 0; j < rb_count; j++) {
+        if (k < K) floating_link_jacobian<T>(M, P, d, rb_first + j - M.robot_first_rb, s_row + threadIdx.x * kStride);
+        __syncthreads();
+        store_staged_rows<kLen>(s_row, n_rows, out + ((size_t)k0 * rb_count + j) * kLen, (size_t)rb_count * kLen);
+        __syncthreads();
+    }
+}
+// out [K][6 + n][6 + n]: floating_mass_matrix of every env.  The tile is one whole matrix per lane: 83 200 B for the 12 joints of
+// anymal - static LDS beyond 64 KiB, one workgroup per CU (gfx950: 160 KiB per workgroup); the routine writes both triangles as it
+// goes, so a row-block store would have to compute the matrix once per block.
+template <class T>
+__global__ __launch_bounds__(kWave) void k_sim_floating_mass_matrix(const DevModel *__restrict__ m, int K, const float *__restrict__ x0_root,
+                                                                    const float *__restrict__ q_, const float *__restrict__ base_,
+                                                                    float *__restrict__ out) {
+    constexpr int kLen = (6 + T::NB) * (6 + T::NB), kStride = staged_stride(kLen);
+    __shared__ float s_row[kWave * kStride];
+    CModel &M = *(CModel *)m;
+    const int k0 = blockIdx.x * kWave, k = k0 + threadIdx.x;
+    const int n_rows = K - k0 < kWave ? K - k0 : kWave;
+    if (k < K) {
+        Pose<T> P;
+        V3 d[T::NB ? T::NB : 1];
+        sim_env_pose<T>(M, K, k, x0_root, q_, base_, P, d);
+        floating_mass_matrix<T>(M, P, d, s_row + threadIdx.x * kStride);
+    }
+    __syncthreads();
+    store_staged_rows<kLen>(s_row, n_rows, out + (size_t)k0 * kLen, kLen);
+}
 
 // Parity / debug entry (mppi_eval_cost): the cost program of the context evaluated by the interpreter the rollout kernels run
 // (program_cost_with, mppi_device.hpp) on CALLER-GIVEN simulator answers - reference-layout rows of n envs - instead of the
@@ -2179,6 +2224,8 @@ struct TopoEntry {
     void (*sim_forward_dynamics)(mppi_ctx *, const float *, int, float *);  // mppi_sim_forward_dynamics
     void (*sim_link_acceleration)(mppi_ctx *, int, int, const float *, int, float *);  // mppi_sim_link_acceleration
     void (*sim_wrench_forces)(mppi_ctx *, int, int, const float *, float *);            // mppi_sim_wrench_forces
+    void (*sim_floating_jacobian)(mppi_ctx *, int, int, float *);  // mppi_sim_floating_jacobian (filled by the contact-scene unit: a moving base is a scene)
+    void (*sim_floating_mass_matrix)(mppi_ctx *, float *);         // mppi_sim_floating_mass_matrix
     hipError_t (*raise_lds)(size_t, size_t);
     size_t (*static_lds)();  // largest static __shared__ footprint among the contact-scene kernels (counts against the 160 KiB too)
 };
@@ -2282,6 +2329,16 @@ template <class T>
 void launch_materialise_scene_t(mppi_ctx *c, float *dof, float *root, float *rb, float *cf) {
     hipLaunchKernelGGL(k_materialise_scene<T>, dim3(c->n_waves), dim3(kWave), 0, c->stream, c->d_model, c->K, c->d_x0_root, c->d_q, c->d_qd, c->d_base,
                        c->d_fr, c->d_cf, dof, root, rb, cf, c->mirror_armed ? c->d_io + kIoDof : nullptr, reinterpret_cast<unsigned *>(c->d_io), c->io_mirror_seq);
+}
+// (a moving base is always a contact-scene context: the base rows are the per-env d_base)
+template <class T>
+void launch_sim_floating_jacobian_t(mppi_ctx *c, int rb_first, int rb_count, float *out) {
+    hipLaunchKernelGGL(k_sim_floating_jacobian<T>, dim3(c->n_waves), dim3(kWave), 0, c->stream, c->d_model, c->K, c->d_x0_root, c->d_q, c->d_base, rb_first,
+                       rb_count, out);
+}
+template <class T>
+void launch_sim_floating_mass_matrix_t(mppi_ctx *c, float *out) {
+    hipLaunchKernelGGL(k_sim_floating_mass_matrix<T>, dim3(c->n_waves), dim3(kWave), 0, c->stream, c->d_model, c->K, c->d_x0_root, c->d_q, c->d_base, out);
 }
 template <class T>
 hipError_t raise_lds_limit(size_t lane_bytes, size_t quad_bytes) {  // lane_bytes == 0: the one-lane kernels are not used
@@ -2443,6 +2500,10 @@ void fill_topo_entry_scene(TopoEntry &e) {
     e.materialise_scene = &launch_materialise_scene_t<T>;
     e.raise_lds = &raise_lds_limit<T>;
     e.static_lds = &static_lds_bytes_scene<T>;
+    if constexpr (T::NBASE == 1) {  // (a forest of several moving bases is refused by both entries: nothing to launch)
+        e.sim_floating_jacobian = &launch_sim_floating_jacobian_t<T>;
+        e.sim_floating_mass_matrix = &launch_sim_floating_mass_matrix_t<T>;
+    }
 }
 
 }  // namespace

@@ -650,6 +650,7 @@ class IsaacGymWrapper:
         self._bias_force = None                         # acquire_bias_force_tensor: filled by refresh_bias_force_tensors()
         self._free_acceleration = None                  # acquire_free_acceleration_tensor: filled by refresh_free_acceleration_tensors()
         self._link_bias_acceleration = {}               # acquire_link_bias_acceleration_tensor: filled by refresh_link_bias_acceleration_tensors()
+        self._floating_jacobians, self._floating_mass_matrix = {}, None   # acquire_floating_*_tensor: filled by refresh_floating_*()
         self._visualize_link_present = sc.viz_link_index() >= 0
         self.visualize_link_buffer = []
         if self._visualize_link_present:
@@ -1025,6 +1026,50 @@ class IsaacGymWrapper:
         rb = self.scene.rigid_body_index(actor_name, link_name)
         out = torch.empty((self.num_envs, 6, self.scene.n_dof), dtype=torch.float32, device=self.device)
         self._physics_call(self._lib.mppi_sim_jacobian, rb, 1, _dev_ptr(out))
+        return out
+
+    # ------------------------------------------------------------------ the same two tensors for a robot with a moving base
+    # gym's tensors of a floating-base actor carry six base columns in front of the joints: generalised velocity (root linvel, root
+    # angvel, qd), world axes - columns 7:13 of the robot's root row, then the joints in DOF order.  mppi_sim_floating_jacobian /
+    # mppi_sim_floating_mass_matrix; a fixed-base robot or a forest of several moving bases raises NotImplementedError with the
+    # library's text (the fixed-base tensors above are the ones to use there).  Link index = rigid-body index within the actor.
+    _FJ_WHAT = "moving-base link Jacobians and the moving-base mass matrix"
+
+    def acquire_floating_jacobian_tensor(self, actor_name: str):
+        """[K, L, 6, 6 + n_dof]: one block per rigid body of the actor (rows 0-2 linear, 3-5 angular, world axes; J @ (root linvel,
+        root angvel, qd) = columns 7:13 of the body's rigid-body row).  Zero until refresh_floating_jacobian_tensors()."""
+        self._live_envs_only(self._FJ_WHAT)
+        if actor_name not in self._floating_jacobians:
+            first, count = self._actor_rb_range(actor_name)
+            t = torch.zeros((self.num_envs, count, 6, 6 + self.scene.n_dof), dtype=torch.float32, device=self.device)
+            self._floating_jacobians[actor_name] = (first, count, t)
+        return self._floating_jacobians[actor_name][2]
+
+    def acquire_floating_mass_matrix_tensor(self, actor_name: str):
+        """[K, 6 + n_dof, 6 + n_dof]: the inertia of every env's robot in (root linvel, root angvel, qd), symmetric, without drive
+        terms.  Zero until refresh_floating_mass_matrix_tensors()."""
+        self._live_envs_only(self._FJ_WHAT)
+        self.scene.actor_index(actor_name)
+        if self._floating_mass_matrix is None:
+            n = 6 + self.scene.n_dof
+            self._floating_mass_matrix = torch.zeros((self.num_envs, n, n), dtype=torch.float32, device=self.device)
+        return self._floating_mass_matrix
+
+    def refresh_floating_jacobian_tensors(self) -> None:
+        self._live_envs_only(self._FJ_WHAT)
+        for first, count, t in self._floating_jacobians.values():
+            self._physics_call(self._lib.mppi_sim_floating_jacobian, first, count, _dev_ptr(t), what=self._FJ_WHAT)
+
+    def refresh_floating_mass_matrix_tensors(self) -> None:
+        self._live_envs_only(self._FJ_WHAT)
+        if self._floating_mass_matrix is not None:
+            self._physics_call(self._lib.mppi_sim_floating_mass_matrix, _dev_ptr(self._floating_mass_matrix), what=self._FJ_WHAT)
+
+    def get_actor_link_floating_jacobian_by_name(self, actor_name: str, link_name: str):
+        """a fresh dense [K, 6, 6 + n_dof] Jacobian of one link (a one-body launch)"""
+        rb = self.scene.rigid_body_index(actor_name, link_name)
+        out = torch.empty((self.num_envs, 6, 6 + self.scene.n_dof), dtype=torch.float32, device=self.device)
+        self._physics_call(self._lib.mppi_sim_floating_jacobian, rb, 1, _dev_ptr(out), what=self._FJ_WHAT)
         return out
 
     # ------------------------------------------------------------------ inverse dynamics and bias forces
