@@ -548,9 +548,29 @@ int mppi_sim_wrench_forces(mppi_ctx_t *ctx, int rb_first, int rb_count, const fl
  * fixed-base forest (use mppi_sim_jacobian / mppi_sim_mass_matrix), a forest of several moving bases (n_extra_bases > 0), a
  * kinematic tree whose launch table lacks the kernel.  Refused before any launch.
  * STILL refused for a moving base: mppi_sim_inverse_dynamics, mppi_sim_forward_dynamics, mppi_sim_link_acceleration and
- * mppi_sim_wrench_forces (they need the bias force of a moving base), and mppi_sim_jacobian / mppi_sim_mass_matrix themselves. */
+ * mppi_sim_wrench_forces, and mppi_sim_jacobian / mppi_sim_mass_matrix themselves; the inverse dynamics of a moving base are
+ * mppi_sim_floating_inverse_dynamics below. */
 int mppi_sim_floating_jacobian(mppi_ctx_t *ctx, int rb_first, int rb_count, float *jac_dev /* [K][rb_count][6][6 + n_dof] */);
 int mppi_sim_floating_mass_matrix(mppi_ctx_t *ctx, float *M_dev /* [K][6 + n_dof][6 + n_dof] */);
+/* What forces a motion TAKES of a robot with a MOVING base, in the generalised velocity v = (root linvel, root angvel, qd) above:
+ *   tau[k] = M(q_k) vd[k]  (left out when vd_dev is NULL)  + C(q_k, v_k) v_k  (with MPPI_ID_VELOCITY)  + g(q_k)  (with MPPI_ID_GRAVITY)
+ * with the M of mppi_sim_floating_mass_matrix, at the envs' current joint positions and rates and at EACH ENV'S OWN base pose and
+ * twist (columns 0:7 and 7:13 of its root row).  vd is the time derivative of v: the acceleration of the root link frame origin
+ * and the angular acceleration, world axes, then the joint accelerations.  tau is the force dual to v, power tau^T v: rows 0-2
+ * the force on the base, rows 3-5 the moment about the base origin, world axes, then the joints in DOF order - gravity
+ * compensation, computed torque, and the base wrench a motion asks for.  A Newton-Euler pass on relative offsets: the result
+ * does not depend on where the base stands (nor on its linear velocity).  Gravity is the model's, as the steps take it; without
+ * it that part is exactly zero.  A part that is not asked for is left out by zeroing its input: separate calls are the very sums
+ * of one call, terms = 0 with a NULL vd_dev writes exact zeros, terms = 0 on vd = e_c gives column c of the mass matrix.
+ * NOT in it: the drives, joint, effort and velocity limits, and CONTACT forces - add J^T f from mppi_sim_floating_jacobian.
+ * One launch on the context's stream - no allocation, no copy, no synchronise: it can sit in a captured graph.  vd_dev and
+ * tau_dev must not overlap.
+ * MPPI_EINVAL: a null tau_dev, unknown bits in terms.  MPPI_EUNSUPPORTED (mppi_last_error says which): a fixed-base robot or
+ * fixed-base forest (use mppi_sim_inverse_dynamics), a forest of several moving bases (n_extra_bases > 0), a kinematic tree whose
+ * launch table lacks the kernel.  Refused before any launch.  Forward dynamics, link accelerations and wrench forces of a moving
+ * base stay refused. */
+int mppi_sim_floating_inverse_dynamics(mppi_ctx_t *ctx, const float *vd_dev /* [K][6 + n_dof] or NULL */, int terms,
+                                       float *tau_dev /* [K][6 + n_dof] */);
 int mppi_sim_accumulate_cost(mppi_ctx_t *ctx, int t, const float *cost_dev); /* S += gamma^t c      */
 int mppi_sim_finish(mppi_ctx_t *ctx);                      /* S += control cost                     */
 /* The same horizon in TWO launches for host-side costs that are functions of the state tensors (mppi_isaac.py:57-69 evaluates

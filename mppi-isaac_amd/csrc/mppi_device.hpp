@@ -1379,7 +1379,8 @@ MPPI_HD void mass_matrix(M &m0, const Pose<T> &P, const V3 *d, float *Mo) { mass
 template <class T, class M>
 MPPI_HD void floating_mass_matrix(M &m0, const Pose<T> &P, const V3 *d, float *Mo) { mass_matrix_blocks<true, T>(m0, P, d, Mo); }
 
-// ---- inverse dynamics of one env of a FIXED-base robot (mppi_sim_inverse_dynamics) ----
+// ---- inverse dynamics of one env: of a FIXED-base robot (mppi_sim_inverse_dynamics) and, with six base rows in front of the
+// ---- joints, of a robot with ONE moving base (mppi_sim_floating_inverse_dynamics) ----
 enum { kIdGravity = 1, kIdVelocity = 2 };  // MPPI_ID_GRAVITY / MPPI_ID_VELOCITY (include/mppi_hip.h)
 
 // tau [NB] = M(q) qdd (qdd null: left out) + C(q, qd) qd (kIdVelocity) + g(q) (kIdGravity; the model's g, and only if gravity_on) at
@@ -1391,14 +1392,31 @@ enum { kIdGravity = 1, kIdVelocity = 2 };  // MPPI_ID_GRAVITY / MPPI_ID_VELOCITY
 // Gravity is the base acceleration -g.  tau is linear in (g, qdd) and quadratic in qd, so a part that is not asked for is left
 // out by zeroing its input: the parts of separate calls are the very sums of one call, and with nothing asked for every product
 // has a zero factor.  The outward pass leaves six values per body (F, N) for the inward one.
-template <class T, class M>
-MPPI_HD void inverse_dynamics(M &m0, const Pose<T> &P, const V3 *d, const float *qd, const float *qdd, int terms, float *tau) {
-    constexpr int NB = T::NB;
+//
+// MOVING = true (floating_inverse_dynamics): qd, qdd and tau are [6 + NB] in the generalised velocity v = (root linvel, root
+// angvel, qd) of floating_link_jacobian - qdd its time derivative (the acceleration of the root frame origin, the angular
+// acceleration, the joint accelerations), tau the force dual to v (rows 0-2 the force on the base, rows 3-5 the moment about the
+// base origin, world axes; power tau^T v), tau = M v' + C v + g with the M of floating_mass_matrix.  The bodies next to the base
+// take the base's (w_b, w_b', a_b - g) as their parent's and ride on it through d[i] = p_i - p_base, the one further offset the
+// floating Jacobian walks; on the way in they hand F and N + d x F on to the base origin, where the base's own rigid body
+// (base_m, base_hb, base_Ic) adds f = m a_b + w' x h + w x (w x h) and n = I_o w' + w x I_o w + h x a_b about its origin.  Rows 0:6
+// are those two sums.  The linear velocity of the base enters nowhere, and neither does its position.
+template <bool MOVING, class T, class M>
+MPPI_HD void inverse_dynamics_pass(M &m0, const Pose<T> &P, const V3 *d, const float *qd, const float *qdd, int terms, float *tau) {
+    constexpr int NB = T::NB, C0 = MOVING ? 6 : 0;
     constexpr int NA = NB ? NB : 1;
     M *mp = &m0;
     const bool with_g = (terms & kIdGravity) != 0 && m0.gravity_on != 0, with_v = (terms & kIdVelocity) != 0;
     const V3 zero = {0.f, 0.f, 0.f};
     const V3 a0 = with_g ? V3{-m0.g[0], -m0.g[1], -m0.g[2]} : zero;
+    V3 wb = zero, wdb = zero, ab = a0;  // MOVING: angular velocity, angular acceleration of the base, acceleration of its origin (- g)
+    if constexpr (MOVING) {
+        if (with_v) wb = V3{qd[3], qd[4], qd[5]};
+        if (qdd != nullptr) {
+            wdb = V3{qdd[3], qdd[4], qdd[5]};
+            ab = a0 + V3{qdd[0], qdd[1], qdd[2]};
+        }
+    }
     V3 w[NA], wd[NA], ao[NA];  // angular velocity, angular acceleration, acceleration of the body origin
     V3 F[NA], N[NA];           // net force, net moment about p_i
     static_for<0, NB>([&](auto ic) MPPI_LAMBDA {
@@ -1409,8 +1427,8 @@ MPPI_HD void inverse_dynamics(M &m0, const Pose<T> &P, const V3 *d, const float 
         const M3 &R = P.R[i];
         const V3 az = {R.a[2], R.a[5], R.a[8]};
         const bool rev = P.jt[i] == 0;
-        const float vi = with_v ? qd[i] : 0.f, ai = qdd != nullptr ? qdd[i] : 0.f;
-        const V3 wp = par < 0 ? zero : w[pj], wdp = par < 0 ? zero : wd[pj], ap = par < 0 ? a0 : ao[pj];
+        const float vi = with_v ? qd[C0 + i] : 0.f, ai = qdd != nullptr ? qdd[C0 + i] : 0.f;
+        const V3 wp = par < 0 ? wb : w[pj], wdp = par < 0 ? wdb : wd[pj], ap = par < 0 ? ab : ao[pj];
         const V3 sv = vi * az, sa = ai * az;
         // the origin rides on the parent at d[i]; a prismatic joint adds its own acceleration and the velocity product 2 w x (qd a)
         V3 acc = ap + cross(wdp, d[i]) + cross(wp, cross(wp, d[i]));
@@ -1440,17 +1458,43 @@ MPPI_HD void inverse_dynamics(M &m0, const Pose<T> &P, const V3 *d, const float 
         F[i] = f;
         N[i] = mul(I, wd[i]) + cross(w[i], mul(I, w[i])) + cross(c, f);
     });
+    V3 Fb = zero, Nb = zero;  // MOVING: net force on the base and net moment about the base origin
+    if constexpr (MOVING) {   // the base's own rigid body
+        const float hb3[3] = {m0.base_hb[0], m0.base_hb[1], m0.base_hb[2]};
+        const float Ic6[6] = {m0.base_Ic[0], m0.base_Ic[1], m0.base_Ic[2], m0.base_Ic[3], m0.base_Ic[4], m0.base_Ic[5]};
+        V3 h;
+        S3 Io;
+        rigid_inertia_about_origin(P.Rb, hb3, Ic6, m0.base_m > 0.f ? 1.f / m0.base_m : 0.f, h, Io);
+        Fb = m0.base_m * ab + cross(wdb, h) + cross(wb, cross(wb, h));
+        Nb = mul(Io, wdb) + cross(wb, mul(Io, wb)) + cross(h, ab);
+    }
     static_rfor<0, NB>([&](auto ic) MPPI_LAMBDA {
         constexpr int i = ic;
         constexpr int par = T::par[i];
         const V3 az = {P.R[i].a[2], P.R[i].a[5], P.R[i].a[8]};
-        tau[i] = P.jt[i] == 0 ? dot(az, N[i]) : dot(az, F[i]);
+        tau[C0 + i] = P.jt[i] == 0 ? dot(az, N[i]) : dot(az, F[i]);
         if constexpr (par >= 0) {  // to the parent's origin: the same force, its moment moved by d[i]
             constexpr int pj = par < 0 ? 0 : par;
             N[pj] = N[pj] + N[i] + cross(d[i], F[i]);
             F[pj] = F[pj] + F[i];
+        } else if constexpr (MOVING) {  // ... and to the base origin
+            Nb = Nb + N[i] + cross(d[i], F[i]);
+            Fb = Fb + F[i];
         }
     });
+    if constexpr (MOVING) {
+        tau[0] = Fb.x; tau[1] = Fb.y; tau[2] = Fb.z;
+        tau[3] = Nb.x; tau[4] = Nb.y; tau[5] = Nb.z;
+    }
+}
+template <class T, class M>
+MPPI_HD void inverse_dynamics(M &m0, const Pose<T> &P, const V3 *d, const float *qd, const float *qdd, int terms, float *tau) {
+    inverse_dynamics_pass<false, T>(m0, P, d, qd, qdd, terms, tau);
+}
+// v [6 + NB] (rows 0-2, the linear velocity of the base, are not read), vd [6 + NB] or null, tau [6 + NB]
+template <class T, class M>
+MPPI_HD void floating_inverse_dynamics(M &m0, const Pose<T> &P, const V3 *d, const float *v, const float *vd, int terms, float *tau) {
+    inverse_dynamics_pass<true, T>(m0, P, d, v, vd, terms, tau);
 }
 
 // ---- forward dynamics of one env of a FIXED-base robot (mppi_sim_forward_dynamics) ----

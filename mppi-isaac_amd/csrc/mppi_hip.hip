@@ -1437,7 +1437,7 @@ int mppi_sim_wrench_forces(mppi_ctx_t *c, int rb_first, int rb_count, const floa
     return launch_check();
 }
 namespace {
-// the launch-table row of a context with ONE moving base, for the two entries that compute the six base columns; everything
+// the launch-table row of a context with ONE moving base, for the entries that compute the six base columns / rows; everything
 // else is refused before any launch, each case with a text of its own
 int floating_entry(mppi_ctx *c, const char *what, const char *fixed_entry, const TopoEntry *&e) {
     if (c->hm.n_bases > 1)
@@ -1472,6 +1472,18 @@ int mppi_sim_floating_mass_matrix(mppi_ctx_t *c, float *M_dev) {
     if (int rc = floating_entry(c, "mppi_sim_floating_mass_matrix", "mppi_sim_mass_matrix", e)) return rc;
     if (!e->sim_floating_mass_matrix) return fail(MPPI_EUNSUPPORTED, "mppi_sim_floating_mass_matrix: not available for this kinematic tree");
     e->sim_floating_mass_matrix(c, M_dev);
+    return launch_check();
+}
+/* tau = M v' + C v + g of a robot with a moving base, in the same generalised velocity: one launch on the context's stream */
+int mppi_sim_floating_inverse_dynamics(mppi_ctx_t *c, const float *vd_dev, int terms, float *tau_dev) {
+    CTX_TRY(c);
+    if (!tau_dev) return fail(MPPI_EINVAL, "mppi_sim_floating_inverse_dynamics: null output");
+    if (terms & ~(MPPI_ID_GRAVITY | MPPI_ID_VELOCITY))
+        return fail(MPPI_EINVAL, "mppi_sim_floating_inverse_dynamics: unknown bits in terms = " + std::to_string(terms) + " (MPPI_ID_GRAVITY | MPPI_ID_VELOCITY)");
+    const TopoEntry *e = nullptr;
+    if (int rc = floating_entry(c, "mppi_sim_floating_inverse_dynamics", "mppi_sim_inverse_dynamics", e)) return rc;
+    if (!e->sim_floating_inverse_dynamics) return fail(MPPI_EUNSUPPORTED, "mppi_sim_floating_inverse_dynamics: not available for this kinematic tree");
+    e->sim_floating_inverse_dynamics(c, vd_dev, terms, tau_dev);
     return launch_check();
 }
 int mppi_sim_accumulate_cost(mppi_ctx_t *c, int t, const float *cost_dev) {

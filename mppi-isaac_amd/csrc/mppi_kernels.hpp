@@ -2028,6 +2028,47 @@ __global__ __launch_bounds__(kWave) void k_sim_floating_mass_matrix(const DevMod
     __syncthreads();
     store_staged_rows<kLen>(s_row, n_rows, out + (size_t)k0 * kLen, kLen);
 }
+// tau [K][6 + n] = M v' (vd_ [K][6 + n], null: left out) + C v + g as `terms` asks (floating_inverse_dynamics, mppi_device.hpp) in the
+// generalised velocity of the two kernels above, v = (root linvel, root angvel, qd).  Every env reads ITS OWN base rows: the pose
+// as sim_env_pose does, the twist - columns 7:13 - here.  The env-major rows of v' come in and the rows of tau go out through one
+// LDS tile, as in k_sim_inverse_dynamics; rows past K - 1 of the last wavefront are neither loaded nor stored.
+template <class T>
+__global__ __launch_bounds__(kWave) void k_sim_floating_inverse_dynamics(const DevModel *__restrict__ m, int K, const float *__restrict__ x0_root,
+                                                                         const float *__restrict__ q_, const float *__restrict__ qd_,
+                                                                         const float *__restrict__ base_, const float *__restrict__ vd_, int terms,
+                                                                         float *__restrict__ out) {
+    constexpr int NB = T::NB, kLen = 6 + NB, kStride = staged_stride(kLen);
+    __shared__ float s_row[kWave * kStride];
+    CModel &M = *(CModel *)m;
+    const int k0 = blockIdx.x * kWave, k = k0 + threadIdx.x;
+    const int n_rows = K - k0 < kWave ? K - k0 : kWave;
+    if (vd_ != nullptr) {
+        load_staged_rows<kLen>(s_row, n_rows, vd_ + (size_t)k0 * kLen, kLen);
+        __syncthreads();
+    }
+    if (k < K) {
+        Pose<T> P;
+        V3 d[NB ? NB : 1];
+        float v[kLen], vd[kLen], tau[kLen];
+        sim_env_pose<T>(M, K, k, x0_root, q_, base_, P, d);
+        for (int j = 0; j < 6; j++) v[j] = base_[(size_t)(7 + j) * K + k];
+        static_for<0, NB>([&](auto ic) {
+            constexpr int i = ic;
+            v[6 + i] = qd_[(size_t)i * K + k];
+        });
+        static_for<0, kLen>([&](auto jc) {
+            constexpr int j = jc;
+            vd[j] = vd_ != nullptr ? s_row[threadIdx.x * kStride + j] : 0.f;
+        });
+        floating_inverse_dynamics<T>(M, P, d, v, vd, terms, tau);  // (v' left out: a zero row - the same sums, as in k_sim_inverse_dynamics)
+        static_for<0, kLen>([&](auto jc) {
+            constexpr int j = jc;
+            s_row[threadIdx.x * kStride + j] = tau[j];
+        });
+    }
+    __syncthreads();
+    store_staged_rows<kLen>(s_row, n_rows, out + (size_t)k0 * kLen, kLen);
+}
 
 // Parity / debug entry (mppi_eval_cost): the cost program of the context evaluated by the interpreter the rollout kernels run
 // (program_cost_with, mppi_device.hpp) on CALLER-GIVEN simulator answers - reference-layout rows of n envs - instead of the
@@ -2226,6 +2267,7 @@ struct TopoEntry {
     void (*sim_wrench_forces)(mppi_ctx *, int, int, const float *, float *);            // mppi_sim_wrench_forces
     void (*sim_floating_jacobian)(mppi_ctx *, int, int, float *);  // mppi_sim_floating_jacobian (filled by the contact-scene unit: a moving base is a scene)
     void (*sim_floating_mass_matrix)(mppi_ctx *, float *);         // mppi_sim_floating_mass_matrix
+    void (*sim_floating_inverse_dynamics)(mppi_ctx *, const float *, int, float *);  // mppi_sim_floating_inverse_dynamics
     hipError_t (*raise_lds)(size_t, size_t);
     size_t (*static_lds)();  // largest static __shared__ footprint among the contact-scene kernels (counts against the 160 KiB too)
 };
@@ -2339,6 +2381,11 @@ void launch_sim_floating_jacobian_t(mppi_ctx *c, int rb_first, int rb_count, flo
 template <class T>
 void launch_sim_floating_mass_matrix_t(mppi_ctx *c, float *out) {
     hipLaunchKernelGGL(k_sim_floating_mass_matrix<T>, dim3(c->n_waves), dim3(kWave), 0, c->stream, c->d_model, c->K, c->d_x0_root, c->d_q, c->d_base, out);
+}
+template <class T>
+void launch_sim_floating_inverse_dynamics_t(mppi_ctx *c, const float *vd, int terms, float *out) {
+    hipLaunchKernelGGL(k_sim_floating_inverse_dynamics<T>, dim3(c->n_waves), dim3(kWave), 0, c->stream, c->d_model, c->K, c->d_x0_root, c->d_q, c->d_qd,
+                       c->d_base, vd, terms, out);
 }
 template <class T>
 hipError_t raise_lds_limit(size_t lane_bytes, size_t quad_bytes) {  // lane_bytes == 0: the one-lane kernels are not used
@@ -2500,9 +2547,10 @@ void fill_topo_entry_scene(TopoEntry &e) {
     e.materialise_scene = &launch_materialise_scene_t<T>;
     e.raise_lds = &raise_lds_limit<T>;
     e.static_lds = &static_lds_bytes_scene<T>;
-    if constexpr (T::NBASE == 1) {  // (a forest of several moving bases is refused by both entries: nothing to launch)
+    if constexpr (T::NBASE == 1) {  // (a forest of several moving bases is refused by the three entries: nothing to launch)
         e.sim_floating_jacobian = &launch_sim_floating_jacobian_t<T>;
         e.sim_floating_mass_matrix = &launch_sim_floating_mass_matrix_t<T>;
+        e.sim_floating_inverse_dynamics = &launch_sim_floating_inverse_dynamics_t<T>;
     }
 }
 

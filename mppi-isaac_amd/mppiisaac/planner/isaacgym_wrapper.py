@@ -651,6 +651,7 @@ class IsaacGymWrapper:
         self._free_acceleration = None                  # acquire_free_acceleration_tensor: filled by refresh_free_acceleration_tensors()
         self._link_bias_acceleration = {}               # acquire_link_bias_acceleration_tensor: filled by refresh_link_bias_acceleration_tensors()
         self._floating_jacobians, self._floating_mass_matrix = {}, None   # acquire_floating_*_tensor: filled by refresh_floating_*()
+        self._floating_bias_force = None                # acquire_floating_bias_force_tensor: filled by refresh_floating_bias_force_tensors()
         self._visualize_link_present = sc.viz_link_index() >= 0
         self.visualize_link_buffer = []
         if self._visualize_link_present:
@@ -1070,6 +1071,44 @@ class IsaacGymWrapper:
         rb = self.scene.rigid_body_index(actor_name, link_name)
         out = torch.empty((self.num_envs, 6, 6 + self.scene.n_dof), dtype=torch.float32, device=self.device)
         self._physics_call(self._lib.mppi_sim_floating_jacobian, rb, 1, _dev_ptr(out), what=self._FJ_WHAT)
+        return out
+
+    # ------------------------------------------------------------------ inverse dynamics and bias forces of a robot with a moving base
+    # tau = M v' + C v + g in the generalised velocity above, [K, 6 + n_dof]: rows 0:3 the force on the base, rows 3:6 the moment
+    # about the base origin (world axes), then the joints (mppi_sim_floating_inverse_dynamics; no drive terms, no limits, no contact
+    # forces).  A fixed-base robot raises NotImplementedError with the library's text: inverse_dynamics below is the one to use.
+    _FID_WHAT = "moving-base inverse dynamics and bias forces"
+
+    def acquire_floating_bias_force_tensor(self, actor_name: str):
+        """[K, 6 + n_dof]: C(q, v) v + g(q) of every env at its own base pose and twist.  Zero until
+        refresh_floating_bias_force_tensors()."""
+        self._live_envs_only(self._FID_WHAT)
+        self.scene.actor_index(actor_name)
+        if self._floating_bias_force is None:
+            self._floating_bias_force = torch.zeros((self.num_envs, 6 + self.scene.n_dof), dtype=torch.float32, device=self.device)
+        return self._floating_bias_force
+
+    def refresh_floating_bias_force_tensors(self) -> None:
+        self._live_envs_only(self._FID_WHAT)
+        if self._floating_bias_force is not None:
+            self._physics_call(self._lib.mppi_sim_floating_inverse_dynamics, None, capi.ID_GRAVITY | capi.ID_VELOCITY,
+                               _dev_ptr(self._floating_bias_force), what=self._FID_WHAT)
+
+    def floating_inverse_dynamics(self, vd=None, gravity=True, velocity=True):
+        """a fresh [K, 6 + n_dof] tensor tau = M v' (vd None: left out) + C v (velocity) + g (gravity).  vd: [6 + n_dof], the same
+        acceleration for every env, or [K, 6 + n_dof]: (acceleration of the root frame origin, angular acceleration, qdd)."""
+        self._live_envs_only(self._FID_WHAT)
+        K, n = self.num_envs, 6 + self.scene.n_dof
+        if vd is not None:
+            vd = torch.as_tensor(vd, dtype=torch.float32, device=self.device)
+            if tuple(vd.shape) == (n,):
+                vd = vd.expand(K, n)
+            elif tuple(vd.shape) != (K, n):
+                raise ValueError(f"vd has shape {tuple(vd.shape)}: expected [{n}] or [{K}, {n}]")
+            vd = vd.contiguous()
+        out = torch.empty((K, n), dtype=torch.float32, device=self.device)
+        terms = (capi.ID_GRAVITY if gravity else 0) | (capi.ID_VELOCITY if velocity else 0)
+        self._physics_call(self._lib.mppi_sim_floating_inverse_dynamics, _dev_ptr(vd), terms, _dev_ptr(out), what=self._FID_WHAT)
         return out
 
     # ------------------------------------------------------------------ inverse dynamics and bias forces
