@@ -547,9 +547,10 @@ int mppi_sim_wrench_forces(mppi_ctx_t *ctx, int rb_first, int rb_count, const fl
  * MPPI_EINVAL: a null output, a range outside [0, n_rb).  MPPI_EUNSUPPORTED (mppi_last_error says which): a fixed-base robot or
  * fixed-base forest (use mppi_sim_jacobian / mppi_sim_mass_matrix), a forest of several moving bases (n_extra_bases > 0), a
  * kinematic tree whose launch table lacks the kernel.  Refused before any launch.
- * STILL refused for a moving base: mppi_sim_inverse_dynamics, mppi_sim_forward_dynamics, mppi_sim_link_acceleration and
- * mppi_sim_wrench_forces, and mppi_sim_jacobian / mppi_sim_mass_matrix themselves; the inverse dynamics of a moving base are
- * mppi_sim_floating_inverse_dynamics below. */
+ * STILL refused for a moving base: mppi_sim_link_acceleration and mppi_sim_wrench_forces (link accelerations and wrench forces
+ * of a moving base have no entry yet), and the fixed-base entries mppi_sim_jacobian / mppi_sim_mass_matrix /
+ * mppi_sim_inverse_dynamics / mppi_sim_forward_dynamics themselves; the inverse and the forward dynamics of a moving base are
+ * mppi_sim_floating_inverse_dynamics and mppi_sim_floating_forward_dynamics below. */
 int mppi_sim_floating_jacobian(mppi_ctx_t *ctx, int rb_first, int rb_count, float *jac_dev /* [K][rb_count][6][6 + n_dof] */);
 int mppi_sim_floating_mass_matrix(mppi_ctx_t *ctx, float *M_dev /* [K][6 + n_dof][6 + n_dof] */);
 /* What forces a motion TAKES of a robot with a MOVING base, in the generalised velocity v = (root linvel, root angvel, qd) above:
@@ -567,10 +568,30 @@ int mppi_sim_floating_mass_matrix(mppi_ctx_t *ctx, float *M_dev /* [K][6 + n_dof
  * tau_dev must not overlap.
  * MPPI_EINVAL: a null tau_dev, unknown bits in terms.  MPPI_EUNSUPPORTED (mppi_last_error says which): a fixed-base robot or
  * fixed-base forest (use mppi_sim_inverse_dynamics), a forest of several moving bases (n_extra_bases > 0), a kinematic tree whose
- * launch table lacks the kernel.  Refused before any launch.  Forward dynamics, link accelerations and wrench forces of a moving
- * base stay refused. */
+ * launch table lacks the kernel.  Refused before any launch.  Link accelerations and wrench forces of a moving base stay refused;
+ * the other direction is mppi_sim_floating_forward_dynamics below. */
 int mppi_sim_floating_inverse_dynamics(mppi_ctx_t *ctx, const float *vd_dev /* [K][6 + n_dof] or NULL */, int terms,
                                        float *tau_dev /* [K][6 + n_dof] */);
+/* What acceleration a base wrench and joint forces GIVE a robot with a MOVING base - the question above in the other direction:
+ *   vd[k] = M(q_k)^-1 ( tau[k]  (zero when tau_dev is NULL)  - C(q_k, v_k) v_k  (with MPPI_ID_VELOCITY)  - g(q_k)  (with MPPI_ID_GRAVITY) )
+ * in the same generalised velocity v = (root linvel, root angvel, qd) with the M of mppi_sim_floating_mass_matrix, at the envs'
+ * current joint positions and rates and at EACH ENV'S OWN base pose and twist (columns 0:7 and 7:13 of its root row).  tau is the
+ * force dual to v: rows 0-2 the force on the base, rows 3-5 the moment about the base origin, world axes, then the joints in DOF
+ * order - to account for a contact force add J^T f from mppi_sim_floating_jacobian.  vd is the time derivative of v: the
+ * acceleration of the root link frame origin and the angular acceleration, world axes, then the joint accelerations.  An
+ * articulated-body solve in O(n_dof) on relative offsets with one 6x6 solve at the base: no matrix M is formed or factored, and
+ * the result does not depend on where the base stands (nor on its linear velocity).  mppi_sim_floating_inverse_dynamics of the
+ * result gives tau back.  terms = 0 on a unit row e_c gives column c of M^-1; terms = 0 with a NULL tau_dev writes exact zeros;
+ * MPPI_ID_GRAVITY alone with a NULL tau_dev is free fall, (g, 0, ..., 0) as numbers; both terms with a NULL tau_dev give the
+ * acceleration of the robot left to itself.  Gravity is the model's, as the steps take it.
+ * NOT in it: the drives, joint, effort and velocity limits, and CONTACT forces.
+ * One launch on the context's stream - no allocation, no copy, no synchronise: it can sit in a captured graph.  tau_dev and
+ * vd_dev must not overlap.
+ * MPPI_EINVAL: a null vd_dev, unknown bits in terms.  MPPI_EUNSUPPORTED (mppi_last_error says which): a fixed-base robot or
+ * fixed-base forest (use mppi_sim_forward_dynamics), a forest of several moving bases (n_extra_bases > 0), a kinematic tree whose
+ * launch table lacks the kernel.  Refused before any launch.  Link accelerations and wrench forces of a moving base stay refused. */
+int mppi_sim_floating_forward_dynamics(mppi_ctx_t *ctx, const float *tau_dev /* [K][6 + n_dof] or NULL */, int terms,
+                                       float *vd_dev /* [K][6 + n_dof] */);
 int mppi_sim_accumulate_cost(mppi_ctx_t *ctx, int t, const float *cost_dev); /* S += gamma^t c      */
 int mppi_sim_finish(mppi_ctx_t *ctx);                      /* S += control cost                     */
 /* The same horizon in TWO launches for host-side costs that are functions of the state tensors (mppi_isaac.py:57-69 evaluates

@@ -1497,7 +1497,8 @@ MPPI_HD void floating_inverse_dynamics(M &m0, const Pose<T> &P, const V3 *d, con
     inverse_dynamics_pass<true, T>(m0, P, d, v, vd, terms, tau);
 }
 
-// ---- forward dynamics of one env of a FIXED-base robot (mppi_sim_forward_dynamics) ----
+// ---- forward dynamics of one env: of a FIXED-base robot (mppi_sim_forward_dynamics) and, with six base rows in front of the
+// ---- joints, of a robot with ONE moving base (mppi_sim_floating_forward_dynamics) ----
 // the articulated inertia A and bias wrench p of a body, both about the body's origin p_i, as seen from the PARENT's origin
 // p_i - dd:  X^T A X and X^T p  with  X (wd, a) = (wd, a + wd x dd).  With Dx = [dd]x:
 //   M' = M,   H' = H + Dx M,   I' = I + Dx H^T + (Dx H'^T)^T   (= I - H Dx + Dx H^T - Dx M Dx),   n' = n + dd x f,  f' = f.
@@ -1520,6 +1521,52 @@ MPPI_HD void shift_to_parent(AI &A, SV &p, V3 dd) {
     p.a = p.a + cross(dd, p.l);
 }
 
+// x [6] = A^-1 b of a symmetric positive definite A = [[I, H], [H^T, M]] (the articulated inertia of a whole robot about the origin of
+// its moving base), unknowns and right-hand side in the order of SV: (angular, linear).  An LDL^T factorisation unrolled in
+// registers: no pivoting (the leading minors of an inertia are positive), constant loop bounds, the reciprocal of the joints.
+MPPI_HD SV solve_spd6(const AI &A, SV b) {
+    const float S[6][6] = {{A.I.xx, A.I.xy, A.I.xz, A.H[0], A.H[1], A.H[2]}, {A.I.xy, A.I.yy, A.I.yz, A.H[3], A.H[4], A.H[5]},
+                           {A.I.xz, A.I.yz, A.I.zz, A.H[6], A.H[7], A.H[8]}, {A.H[0], A.H[3], A.H[6], A.M.xx, A.M.xy, A.M.xz},
+                           {A.H[1], A.H[4], A.H[7], A.M.xy, A.M.yy, A.M.yz}, {A.H[2], A.H[5], A.H[8], A.M.xz, A.M.yz, A.M.zz}};
+    float L[6][6], W[6][6], rd[6];  // unit lower L, W = L D (strictly lower parts only), 1 / D
+    float x[6] = {b.a.x, b.a.y, b.a.z, b.l.x, b.l.y, b.l.z};
+    static_for<0, 6>([&](auto jc) MPPI_LAMBDA {
+        constexpr int j = jc;
+        float dj = S[j][j];
+        static_for<0, j>([&](auto kc) MPPI_LAMBDA {
+            constexpr int k = kc;
+            dj -= L[j][k] * W[j][k];
+        });
+        rd[j] = frcp(dj);
+        static_for<j + 1, 6>([&](auto ic) MPPI_LAMBDA {
+            constexpr int i = ic;
+            float wij = S[i][j];
+            static_for<0, j>([&](auto kc) MPPI_LAMBDA {
+                constexpr int k = kc;
+                wij -= W[i][k] * L[j][k];
+            });
+            W[i][j] = wij;
+            L[i][j] = wij * rd[j];
+        });
+    });
+    static_for<0, 6>([&](auto ic) MPPI_LAMBDA {  // L y = b
+        constexpr int i = ic;
+        static_for<0, i>([&](auto kc) MPPI_LAMBDA {
+            constexpr int k = kc;
+            x[i] -= L[i][k] * x[k];
+        });
+    });
+    static_rfor<0, 6>([&](auto ic) MPPI_LAMBDA {  // D L^T x = y
+        constexpr int i = ic;
+        x[i] *= rd[i];
+        static_for<i + 1, 6>([&](auto kc) MPPI_LAMBDA {
+            constexpr int k = kc;
+            x[i] -= L[k][i] * x[k];
+        });
+    });
+    return {{x[0], x[1], x[2]}, {x[3], x[4], x[5]}};
+}
+
 // qdd [NB] = M(q)^-1 (tau (null: zero) - C(q, qd) qd (kIdVelocity) - g(q) (kIdGravity; the model's g, and only if gravity_on)) at the
 // body poses P: forward dynamics of the plain rigid-body model of inverse_dynamics - no drive terms, no limits, no contacts.  A
 // three-pass articulated-body solve in world axes under the rule of mass_matrix: the articulated inertia (symmetric I, general H,
@@ -1530,9 +1577,19 @@ MPPI_HD void shift_to_parent(AI &A, SV &p, V3 dd) {
 // of a revolute joint, (0, w_p x (w_p x d) + 2 w_p x qd a) of a prismatic one, and a body's bias wrench is (w x I w, w x (w x h)).
 // A part that is not asked for is left out by zeroing its input (qd -> 0, the base acceleration -> 0), as there: the result with
 // qd = 0 is the result without kIdVelocity bit for bit, and with nothing asked for and no tau every product has a zero factor.
-template <class T, class M>
-MPPI_HD void forward_dynamics(M &m0, const Pose<T> &P, const V3 *d, const float *qd, const float *tau, int terms, float *qdd) {
-    constexpr int NB = T::NB;
+//
+// MOVING = true (floating_forward_dynamics): qd, tau and qdd are [6 + NB] in the generalised velocity v = (root linvel, root angvel,
+// qd) of floating_inverse_dynamics - tau the force dual to v (rows 0-2 the force on the base, rows 3-5 the moment about the base
+// origin, world axes), qdd the time derivative of v - and qdd = M^-1 (tau - C v - g) with the M of floating_mass_matrix.  The bodies
+// next to the base start from the base's angular velocity and hand their subtrees, joint left free, on to the base origin through
+// d[i] = p_i - p_base exactly as to a parent; there the base's own rigid body (base_m, base_hb, base_Ic) joins them and the 6x6
+// system  A_b (w_b', a') = (tau[3:6], tau[0:3]) - p_b  gives the base's angular acceleration and the acceleration a' of its origin in
+// the frame that falls with -g (ab of inverse_dynamics_pass): rows 0-2 are a' + g, and the outward pass starts from (w_b, w_b', a').
+// Gravity enters in that one sum only - without tau and velocity the system has a zero right-hand side and the result is free fall,
+// (g, 0, ..., 0) as numbers.  The linear velocity of the base enters nowhere, and neither does its position.
+template <bool MOVING, class T, class M>
+MPPI_HD void forward_dynamics_pass(M &m0, const Pose<T> &P, const V3 *d, const float *qd, const float *tau, int terms, float *qdd) {
+    constexpr int NB = T::NB, C0 = MOVING ? 6 : 0;
     constexpr int NA = NB ? NB : 1;
     M *mp = &m0;
     const bool with_g = (terms & kIdGravity) != 0 && m0.gravity_on != 0, with_v = (terms & kIdVelocity) != 0;
@@ -1543,14 +1600,20 @@ MPPI_HD void forward_dynamics(M &m0, const Pose<T> &P, const V3 *d, const float 
     float invd[NA], u[NA];   // 1 / (S^T A S),  tau - S^T p
     AI accA[NA];             // the children's articulated inertias and bias wrenches, about the parent's origin
     SV accp[NA];
+    V3 wb = zero;            // MOVING: angular velocity of the base
+    AI Ab;                   // MOVING: articulated inertia and bias wrench of the whole robot about the base origin
+    SV pb = {zero, zero};
+    if constexpr (MOVING) {
+        if (with_v) wb = V3{qd[3], qd[4], qd[5]};
+    }
     // pass 1: angular velocities, base to leaves
     static_for<0, NB>([&](auto ic) MPPI_LAMBDA {
         constexpr int i = ic;
         constexpr int par = T::par[i];
         constexpr int pj = par < 0 ? 0 : par;
         const V3 az = {P.R[i].a[2], P.R[i].a[5], P.R[i].a[8]};
-        const float vi = with_v ? qd[i] : 0.f;
-        const V3 wp = par < 0 ? zero : w[pj];
+        const float vi = with_v ? qd[C0 + i] : 0.f;
+        const V3 wp = par < 0 ? (MOVING ? wb : zero) : w[pj];  // (the fixed front keeps its constant: its generated code is the one it had)
         w[i] = P.jt[i] == 0 ? wp + vi * az : wp;
     });
     // pass 2: articulated inertias and bias wrenches, leaves to base
@@ -1593,12 +1656,12 @@ MPPI_HD void forward_dynamics(M &m0, const Pose<T> &P, const V3 *d, const float 
         const SV S = rev ? SV{az, zero} : SV{zero, az};
         U[i] = mul(A, S);
         invd[i] = frcp(dot(S, U[i]));
-        u[i] = (tau != nullptr ? tau[i] : 0.f) - dot(S, p);
-        if constexpr (par >= 0) {
+        u[i] = (tau != nullptr ? tau[C0 + i] : 0.f) - dot(S, p);
+        if constexpr (par >= 0 || MOVING) {
             // what the parent sees of this subtree with joint i left free:  A - U U^T / D,  p + (A - U U^T / D) c + U u / D
             constexpr int pj = par < 0 ? 0 : par;
-            const V3 wp = w[pj];
-            const V3 sv = (with_v ? qd[i] : 0.f) * az;
+            const V3 wp = par < 0 ? (MOVING ? wb : zero) : w[pj];
+            const V3 sv = (with_v ? qd[C0 + i] : 0.f) * az;
             const V3 cen = cross(wp, cross(wp, d[i]));
             const SV cv = rev ? SV{cross(wp, sv), cen} : SV{zero, cen + 2.f * cross(wp, sv)};
             rank1_sub(A, U[i], invd[i]);
@@ -1606,7 +1669,15 @@ MPPI_HD void forward_dynamics(M &m0, const Pose<T> &P, const V3 *d, const float 
             const float k = u[i] * invd[i];
             SV pa = {p.a + Ac.a + k * U[i].a, p.l + Ac.l + k * U[i].l};
             shift_to_parent(A, pa, d[i]);
-            if constexpr (last_child<T>(pj) == i) {
+            if constexpr (par < 0) {  // (MOVING) ... the base is that parent: about the base origin
+                if constexpr (last_child<T>(-1) == i) {
+                    Ab = A;
+                    pb = pa;
+                } else {
+                    add_to(Ab, A);
+                    pb = pb + pa;
+                }
+            } else if constexpr (last_child<T>(pj) == i) {
                 accA[pj] = A;
                 accp[pj] = pa;
             } else {
@@ -1615,6 +1686,33 @@ MPPI_HD void forward_dynamics(M &m0, const Pose<T> &P, const V3 *d, const float 
             }
         }
     });
+    V3 wdb = zero, ab = a0;  // MOVING: angular acceleration of the base, acceleration of its origin (- g)
+    if constexpr (MOVING) {
+        // the base's own rigid body, then the base as the one body without a joint: all six accelerations are free
+        const float hb3[3] = {m0.base_hb[0], m0.base_hb[1], m0.base_hb[2]};
+        const float Ic6[6] = {m0.base_Ic[0], m0.base_Ic[1], m0.base_Ic[2], m0.base_Ic[3], m0.base_Ic[4], m0.base_Ic[5]};
+        V3 h;
+        AI B;
+        rigid_inertia_about_origin(P.Rb, hb3, Ic6, m0.base_m > 0.f ? 1.f / m0.base_m : 0.f, h, B.I);
+        B.H[0] = 0.f;  B.H[1] = -h.z; B.H[2] = h.y;
+        B.H[3] = h.z;  B.H[4] = 0.f;  B.H[5] = -h.x;
+        B.H[6] = -h.y; B.H[7] = h.x;  B.H[8] = 0.f;
+        B.M = {m0.base_m, 0.f, 0.f, m0.base_m, 0.f, m0.base_m};
+        const SV pr = {cross(wb, mul(B.I, wb)), cross(wb, cross(wb, h))};
+        if constexpr (last_child<T>(-1) >= 0) {
+            add_to(Ab, B);
+            pb = pb + pr;
+        } else {
+            Ab = B;
+            pb = pr;
+        }
+        const V3 fb = tau != nullptr ? V3{tau[0], tau[1], tau[2]} : zero, nb = tau != nullptr ? V3{tau[3], tau[4], tau[5]} : zero;
+        const SV acc = solve_spd6(Ab, SV{nb - pb.a, fb - pb.l});
+        wdb = acc.a;
+        ab = acc.l;
+        qdd[0] = ab.x - a0.x; qdd[1] = ab.y - a0.y; qdd[2] = ab.z - a0.z;
+        qdd[3] = wdb.x; qdd[4] = wdb.y; qdd[5] = wdb.z;
+    }
     // pass 3: accelerations, base to leaves.  Gravity is the base acceleration -g.
     V3 wd[NA], ao[NA];  // angular acceleration, acceleration of the body origin
     static_for<0, NB>([&](auto ic) MPPI_LAMBDA {
@@ -1623,17 +1721,26 @@ MPPI_HD void forward_dynamics(M &m0, const Pose<T> &P, const V3 *d, const float 
         constexpr int pj = par < 0 ? 0 : par;
         const V3 az = {P.R[i].a[2], P.R[i].a[5], P.R[i].a[8]};
         const bool rev = P.jt[i] == 0;
-        const V3 wp = par < 0 ? zero : w[pj], wdp = par < 0 ? zero : wd[pj], ap = par < 0 ? a0 : ao[pj];
-        const V3 sv = (with_v ? qd[i] : 0.f) * az;
+        const V3 wp = par < 0 ? (MOVING ? wb : zero) : w[pj], wdp = par < 0 ? (MOVING ? wdb : zero) : wd[pj], ap = par < 0 ? (MOVING ? ab : a0) : ao[pj];
+        const V3 sv = (with_v ? qd[C0 + i] : 0.f) * az;
         // the origin rides on the parent at d[i]; the joint's velocity products, as in inverse_dynamics
         V3 acc = ap + cross(wdp, d[i]) + cross(wp, cross(wp, d[i]));
         if (!rev) acc = acc + 2.f * cross(wp, sv);
         const V3 ang = rev ? wdp + cross(wp, sv) : wdp;
         const float dd = (u[i] - dot(U[i], SV{ang, acc})) * invd[i];
-        qdd[i] = dd;
+        qdd[C0 + i] = dd;
         wd[i] = rev ? ang + dd * az : ang;
         ao[i] = rev ? acc : acc + dd * az;
     });
+}
+template <class T, class M>
+MPPI_HD void forward_dynamics(M &m0, const Pose<T> &P, const V3 *d, const float *qd, const float *tau, int terms, float *qdd) {
+    forward_dynamics_pass<false, T>(m0, P, d, qd, tau, terms, qdd);
+}
+// v [6 + NB] (rows 0-2, the linear velocity of the base, are not read), tau [6 + NB] or null, vd [6 + NB]
+template <class T, class M>
+MPPI_HD void floating_forward_dynamics(M &m0, const Pose<T> &P, const V3 *d, const float *v, const float *tau, int terms, float *vd) {
+    forward_dynamics_pass<true, T>(m0, P, d, v, tau, terms, vd);
 }
 
 // ---- link accelerations and the joint forces of link wrenches of one env of a FIXED-base robot ----

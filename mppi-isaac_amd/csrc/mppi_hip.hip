@@ -1486,6 +1486,18 @@ int mppi_sim_floating_inverse_dynamics(mppi_ctx_t *c, const float *vd_dev, int t
     e->sim_floating_inverse_dynamics(c, vd_dev, terms, tau_dev);
     return launch_check();
 }
+/* v' = M^-1 (tau - C v - g) of a robot with a moving base, in the same generalised velocity: one launch on the context's stream */
+int mppi_sim_floating_forward_dynamics(mppi_ctx_t *c, const float *tau_dev, int terms, float *vd_dev) {
+    CTX_TRY(c);
+    if (!vd_dev) return fail(MPPI_EINVAL, "mppi_sim_floating_forward_dynamics: null output");
+    if (terms & ~(MPPI_ID_GRAVITY | MPPI_ID_VELOCITY))
+        return fail(MPPI_EINVAL, "mppi_sim_floating_forward_dynamics: unknown bits in terms = " + std::to_string(terms) + " (MPPI_ID_GRAVITY | MPPI_ID_VELOCITY)");
+    const TopoEntry *e = nullptr;
+    if (int rc = floating_entry(c, "mppi_sim_floating_forward_dynamics", "mppi_sim_forward_dynamics", e)) return rc;
+    if (!e->sim_floating_forward_dynamics) return fail(MPPI_EUNSUPPORTED, "mppi_sim_floating_forward_dynamics: not available for this kinematic tree");
+    e->sim_floating_forward_dynamics(c, tau_dev, terms, vd_dev);
+    return launch_check();
+}
 int mppi_sim_accumulate_cost(mppi_ctx_t *c, int t, const float *cost_dev) {
     CTX_TRY(c);
     if (!cost_dev) return fail(MPPI_EINVAL, "null cost");

@@ -2069,6 +2069,46 @@ __global__ __launch_bounds__(kWave) void k_sim_floating_inverse_dynamics(const D
     __syncthreads();
     store_staged_rows<kLen>(s_row, n_rows, out + (size_t)k0 * kLen, kLen);
 }
+// vd [K][6 + n] = M^-1 (tau (tau_ [K][6 + n], null: zero) - C v - g as `terms` asks) (floating_forward_dynamics, mppi_device.hpp): the
+// kernel above with the roles exchanged, in the same generalised velocity, through the same tile with the same two barriers.
+// Every env reads its own base pose and twist; rows past K - 1 of the last wavefront are neither loaded nor stored.
+template <class T>
+__global__ __launch_bounds__(kWave) void k_sim_floating_forward_dynamics(const DevModel *__restrict__ m, int K, const float *__restrict__ x0_root,
+                                                                         const float *__restrict__ q_, const float *__restrict__ qd_,
+                                                                         const float *__restrict__ base_, const float *__restrict__ tau_, int terms,
+                                                                         float *__restrict__ out) {
+    constexpr int NB = T::NB, kLen = 6 + NB, kStride = staged_stride(kLen);
+    __shared__ float s_row[kWave * kStride];
+    CModel &M = *(CModel *)m;
+    const int k0 = blockIdx.x * kWave, k = k0 + threadIdx.x;
+    const int n_rows = K - k0 < kWave ? K - k0 : kWave;
+    if (tau_ != nullptr) {
+        load_staged_rows<kLen>(s_row, n_rows, tau_ + (size_t)k0 * kLen, kLen);
+        __syncthreads();
+    }
+    if (k < K) {
+        Pose<T> P;
+        V3 d[NB ? NB : 1];
+        float v[kLen], tau[kLen], vd[kLen];
+        sim_env_pose<T>(M, K, k, x0_root, q_, base_, P, d);
+        for (int j = 0; j < 6; j++) v[j] = base_[(size_t)(7 + j) * K + k];
+        static_for<0, NB>([&](auto ic) {
+            constexpr int i = ic;
+            v[6 + i] = qd_[(size_t)i * K + k];
+        });
+        static_for<0, kLen>([&](auto jc) {
+            constexpr int j = jc;
+            tau[j] = tau_ != nullptr ? s_row[threadIdx.x * kStride + j] : 0.f;
+        });
+        floating_forward_dynamics<T>(M, P, d, v, tau, terms, vd);  // (tau left out: a zero row - the same sums, as in k_sim_forward_dynamics)
+        static_for<0, kLen>([&](auto jc) {
+            constexpr int j = jc;
+            s_row[threadIdx.x * kStride + j] = vd[j];
+        });
+    }
+    __syncthreads();
+    store_staged_rows<kLen>(s_row, n_rows, out + (size_t)k0 * kLen, kLen);
+}
 
 // Parity / debug entry (mppi_eval_cost): the cost program of the context evaluated by the interpreter the rollout kernels run
 // (program_cost_with, mppi_device.hpp) on CALLER-GIVEN simulator answers - reference-layout rows of n envs - instead of the
@@ -2268,6 +2308,7 @@ struct TopoEntry {
     void (*sim_floating_jacobian)(mppi_ctx *, int, int, float *);  // mppi_sim_floating_jacobian (filled by the contact-scene unit: a moving base is a scene)
     void (*sim_floating_mass_matrix)(mppi_ctx *, float *);         // mppi_sim_floating_mass_matrix
     void (*sim_floating_inverse_dynamics)(mppi_ctx *, const float *, int, float *);  // mppi_sim_floating_inverse_dynamics
+    void (*sim_floating_forward_dynamics)(mppi_ctx *, const float *, int, float *);  // mppi_sim_floating_forward_dynamics
     hipError_t (*raise_lds)(size_t, size_t);
     size_t (*static_lds)();  // largest static __shared__ footprint among the contact-scene kernels (counts against the 160 KiB too)
 };
@@ -2386,6 +2427,11 @@ template <class T>
 void launch_sim_floating_inverse_dynamics_t(mppi_ctx *c, const float *vd, int terms, float *out) {
     hipLaunchKernelGGL(k_sim_floating_inverse_dynamics<T>, dim3(c->n_waves), dim3(kWave), 0, c->stream, c->d_model, c->K, c->d_x0_root, c->d_q, c->d_qd,
                        c->d_base, vd, terms, out);
+}
+template <class T>
+void launch_sim_floating_forward_dynamics_t(mppi_ctx *c, const float *tau, int terms, float *out) {
+    hipLaunchKernelGGL(k_sim_floating_forward_dynamics<T>, dim3(c->n_waves), dim3(kWave), 0, c->stream, c->d_model, c->K, c->d_x0_root, c->d_q, c->d_qd,
+                       c->d_base, tau, terms, out);
 }
 template <class T>
 hipError_t raise_lds_limit(size_t lane_bytes, size_t quad_bytes) {  // lane_bytes == 0: the one-lane kernels are not used
@@ -2547,10 +2593,11 @@ void fill_topo_entry_scene(TopoEntry &e) {
     e.materialise_scene = &launch_materialise_scene_t<T>;
     e.raise_lds = &raise_lds_limit<T>;
     e.static_lds = &static_lds_bytes_scene<T>;
-    if constexpr (T::NBASE == 1) {  // (a forest of several moving bases is refused by the three entries: nothing to launch)
+    if constexpr (T::NBASE == 1) {  // (a forest of several moving bases is refused by the four entries: nothing to launch)
         e.sim_floating_jacobian = &launch_sim_floating_jacobian_t<T>;
         e.sim_floating_mass_matrix = &launch_sim_floating_mass_matrix_t<T>;
         e.sim_floating_inverse_dynamics = &launch_sim_floating_inverse_dynamics_t<T>;
+        e.sim_floating_forward_dynamics = &launch_sim_floating_forward_dynamics_t<T>;
     }
 }
 

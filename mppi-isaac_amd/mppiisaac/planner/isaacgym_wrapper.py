@@ -652,6 +652,7 @@ class IsaacGymWrapper:
         self._link_bias_acceleration = {}               # acquire_link_bias_acceleration_tensor: filled by refresh_link_bias_acceleration_tensors()
         self._floating_jacobians, self._floating_mass_matrix = {}, None   # acquire_floating_*_tensor: filled by refresh_floating_*()
         self._floating_bias_force = None                # acquire_floating_bias_force_tensor: filled by refresh_floating_bias_force_tensors()
+        self._floating_free_acceleration = None         # acquire_floating_free_acceleration_tensor: filled by refresh_floating_free_acceleration_tensors()
         self._visualize_link_present = sc.viz_link_index() >= 0
         self.visualize_link_buffer = []
         if self._visualize_link_present:
@@ -1110,6 +1111,57 @@ class IsaacGymWrapper:
         terms = (capi.ID_GRAVITY if gravity else 0) | (capi.ID_VELOCITY if velocity else 0)
         self._physics_call(self._lib.mppi_sim_floating_inverse_dynamics, _dev_ptr(vd), terms, _dev_ptr(out), what=self._FID_WHAT)
         return out
+
+    # ------------------------------------------------------------------ forward dynamics, free acceleration and M^-1 of a robot with a moving base
+    # v' = M^-1 (tau - C v - g) in the same generalised velocity, [K, 6 + n_dof]: rows 0:3 the acceleration of the root frame origin,
+    # rows 3:6 the angular acceleration (world axes), then the joints (mppi_sim_floating_forward_dynamics: an articulated-body solve
+    # with one 6x6 solve at the base; no drive terms, no limits, no contact forces - add J^T f to tau).  A fixed-base robot raises
+    # NotImplementedError with the library's text: forward_dynamics below is the one to use.
+    _FFD_WHAT = "moving-base forward dynamics and free accelerations"
+
+    def floating_forward_dynamics(self, tau=None, gravity=True, velocity=True):
+        """a fresh [K, 6 + n_dof] tensor v' = M^-1 (tau (None: zero) - C v (velocity) - g (gravity)).  tau: [6 + n_dof], the same
+        force for every env, or [K, 6 + n_dof]: (force on the base, moment about the base origin, joint forces)."""
+        self._live_envs_only(self._FFD_WHAT)
+        K, n = self.num_envs, 6 + self.scene.n_dof
+        if tau is not None:
+            tau = torch.as_tensor(tau, dtype=torch.float32, device=self.device)
+            if tuple(tau.shape) == (n,):
+                tau = tau.expand(K, n)
+            elif tuple(tau.shape) != (K, n):
+                raise ValueError(f"tau has shape {tuple(tau.shape)}: expected [{n}] or [{K}, {n}]")
+            tau = tau.contiguous()
+        out = torch.empty((K, n), dtype=torch.float32, device=self.device)
+        terms = (capi.ID_GRAVITY if gravity else 0) | (capi.ID_VELOCITY if velocity else 0)
+        self._physics_call(self._lib.mppi_sim_floating_forward_dynamics, _dev_ptr(tau), terms, _dev_ptr(out), what=self._FFD_WHAT)
+        return out
+
+    def acquire_floating_free_acceleration_tensor(self, actor_name: str):
+        """[K, 6 + n_dof]: -M^-1 (C v + g) of every env at its own base pose and twist - how the robot accelerates when nothing
+        pushes it.  Zero until refresh_floating_free_acceleration_tensors()."""
+        self._live_envs_only(self._FFD_WHAT)
+        self.scene.actor_index(actor_name)
+        if self._floating_free_acceleration is None:
+            self._floating_free_acceleration = torch.zeros((self.num_envs, 6 + self.scene.n_dof), dtype=torch.float32, device=self.device)
+        return self._floating_free_acceleration
+
+    def refresh_floating_free_acceleration_tensors(self) -> None:
+        self._live_envs_only(self._FFD_WHAT)
+        if self._floating_free_acceleration is not None:
+            self._physics_call(self._lib.mppi_sim_floating_forward_dynamics, None, capi.ID_GRAVITY | capi.ID_VELOCITY,
+                               _dev_ptr(self._floating_free_acceleration), what=self._FFD_WHAT)
+
+    def floating_inverse_mass_matrix(self):
+        """a fresh [K, 6 + n_dof, 6 + n_dof] tensor M^-1 of every env: 6 + n_dof launches on the unit rows with neither gravity nor
+        velocity terms.  Written symmetric from the lower triangle, so it is symmetric bit for bit like M."""
+        self._live_envs_only(self._FFD_WHAT)
+        K, n = self.num_envs, 6 + self.scene.n_dof
+        cols = torch.empty((n, K, n), dtype=torch.float32, device=self.device)      # cols[c, k, :] = M^-1 e_c of env k
+        units = torch.eye(n, dtype=torch.float32, device=self.device)[:, None, :].expand(n, K, n).contiguous()
+        for c in range(n):
+            self._physics_call(self._lib.mppi_sim_floating_forward_dynamics, _dev_ptr(units[c]), 0, _dev_ptr(cols[c]), what=self._FFD_WHAT)
+        low = torch.tril(cols.permute(1, 2, 0))      # [K, row, column]
+        return low + torch.tril(low, -1).transpose(1, 2)
 
     # ------------------------------------------------------------------ inverse dynamics and bias forces
     # What joint forces a motion takes: tau = M(q) qdd + C(q, qd) qd + g(q) of every env at its current joint positions and rates
