@@ -547,10 +547,11 @@ int mppi_sim_wrench_forces(mppi_ctx_t *ctx, int rb_first, int rb_count, const fl
  * MPPI_EINVAL: a null output, a range outside [0, n_rb).  MPPI_EUNSUPPORTED (mppi_last_error says which): a fixed-base robot or
  * fixed-base forest (use mppi_sim_jacobian / mppi_sim_mass_matrix), a forest of several moving bases (n_extra_bases > 0), a
  * kinematic tree whose launch table lacks the kernel.  Refused before any launch.
- * STILL refused for a moving base: mppi_sim_link_acceleration and mppi_sim_wrench_forces (link accelerations and wrench forces
- * of a moving base have no entry yet), and the fixed-base entries mppi_sim_jacobian / mppi_sim_mass_matrix /
+ * STILL refused for a moving base: mppi_sim_link_acceleration and mppi_sim_wrench_forces (a moving base has entries of its own for
+ * both, at the end of this group), and the fixed-base entries mppi_sim_jacobian / mppi_sim_mass_matrix /
  * mppi_sim_inverse_dynamics / mppi_sim_forward_dynamics themselves; the inverse and the forward dynamics of a moving base are
- * mppi_sim_floating_inverse_dynamics and mppi_sim_floating_forward_dynamics below. */
+ * mppi_sim_floating_inverse_dynamics and mppi_sim_floating_forward_dynamics below, link accelerations and wrench forces
+ * mppi_sim_floating_link_acceleration and mppi_sim_floating_wrench_forces after them. */
 int mppi_sim_floating_jacobian(mppi_ctx_t *ctx, int rb_first, int rb_count, float *jac_dev /* [K][rb_count][6][6 + n_dof] */);
 int mppi_sim_floating_mass_matrix(mppi_ctx_t *ctx, float *M_dev /* [K][6 + n_dof][6 + n_dof] */);
 /* What forces a motion TAKES of a robot with a MOVING base, in the generalised velocity v = (root linvel, root angvel, qd) above:
@@ -568,8 +569,9 @@ int mppi_sim_floating_mass_matrix(mppi_ctx_t *ctx, float *M_dev /* [K][6 + n_dof
  * tau_dev must not overlap.
  * MPPI_EINVAL: a null tau_dev, unknown bits in terms.  MPPI_EUNSUPPORTED (mppi_last_error says which): a fixed-base robot or
  * fixed-base forest (use mppi_sim_inverse_dynamics), a forest of several moving bases (n_extra_bases > 0), a kinematic tree whose
- * launch table lacks the kernel.  Refused before any launch.  Link accelerations and wrench forces of a moving base stay refused;
- * the other direction is mppi_sim_floating_forward_dynamics below. */
+ * launch table lacks the kernel.  Refused before any launch.  The fixed-base entries mppi_sim_link_acceleration and
+ * mppi_sim_wrench_forces stay refused for a moving base: use mppi_sim_floating_link_acceleration / mppi_sim_floating_wrench_forces
+ * below; the other direction is mppi_sim_floating_forward_dynamics below. */
 int mppi_sim_floating_inverse_dynamics(mppi_ctx_t *ctx, const float *vd_dev /* [K][6 + n_dof] or NULL */, int terms,
                                        float *tau_dev /* [K][6 + n_dof] */);
 /* What acceleration a base wrench and joint forces GIVE a robot with a MOVING base - the question above in the other direction:
@@ -589,9 +591,42 @@ int mppi_sim_floating_inverse_dynamics(mppi_ctx_t *ctx, const float *vd_dev /* [
  * vd_dev must not overlap.
  * MPPI_EINVAL: a null vd_dev, unknown bits in terms.  MPPI_EUNSUPPORTED (mppi_last_error says which): a fixed-base robot or
  * fixed-base forest (use mppi_sim_forward_dynamics), a forest of several moving bases (n_extra_bases > 0), a kinematic tree whose
- * launch table lacks the kernel.  Refused before any launch.  Link accelerations and wrench forces of a moving base stay refused. */
+ * launch table lacks the kernel.  Refused before any launch.  The fixed-base entries mppi_sim_link_acceleration and
+ * mppi_sim_wrench_forces stay refused for a moving base: use mppi_sim_floating_link_acceleration / mppi_sim_floating_wrench_forces
+ * below. */
 int mppi_sim_floating_forward_dynamics(mppi_ctx_t *ctx, const float *tau_dev /* [K][6 + n_dof] or NULL */, int terms,
                                        float *vd_dev /* [K][6 + n_dof] */);
+/* How a link of a robot with a MOVING base ACCELERATES, and what a wrench on a link asks of the base and the joints - what
+ * mppi_sim_link_acceleration and mppi_sim_wrench_forces are for a fixed base, in the generalised velocity v = (root linvel, root
+ * angvel, qd) and with the J of mppi_sim_floating_jacobian: world axes, rows 0-2 linear (the link frame origin), rows 3-5 angular,
+ * the block index is the rigid-body index, env-major device tensors.  v is read from EACH ENV'S OWN base rows (columns 7:13 of its
+ * root row) and joint rates; vd is its time derivative (the acceleration of the root link frame origin and the angular acceleration,
+ * world axes, then the joint accelerations).
+ *   acc[k][b] = J_b vd[k]  (left out when vd_dev is NULL)  + Jdot_b v_k  (with MPPI_ID_VELOCITY)
+ * - the time derivative of columns 7:13 of the body's rigid-body row along the motion (v, vd): rows 0-2 the classical acceleration
+ * of the link frame origin, rows 3-5 the angular acceleration.  A kinematic quantity: gravity has no part in it, MPPI_ID_GRAVITY or
+ * any other bit in terms is MPPI_EINVAL.  A part that is not asked for is left out by zeroing its input: separate calls are the
+ * very sums of one call, terms = 0 with a NULL vd_dev writes exact zeros, terms = 0 on vd = e_c gives column c of J_b.  Links
+ * welded to the moving base accelerate with it, a_b + wd_b x r + w_b x (w_b x r) and wd_b with r = R_base link.p; bodies of box /
+ * sphere actors get exact zero rows.  One outward pass of the Newton-Euler recursion on relative offsets: nothing is a difference
+ * of world positions, and the result does not depend on where the base stands (nor on its linear velocity).  vd_dev and acc_dev
+ * must not overlap.
+ *   tau[k] = sum_b J_b^T w[k][b],  w = (force on the link, moment about the link frame origin), world axes - the force dual to v:
+ * rows 0-2 the total force on the base, rows 3-5 the total moment about the base origin, then the joints in DOF order;
+ * tau . v = sum_b w_b . (J_b v).  This is the J^T f of a contact force: ADD it to a tau given to mppi_sim_floating_forward_dynamics,
+ * or SUBTRACT it from what mppi_sim_floating_inverse_dynamics returns.  The wrenches on links welded to the base go to rows 0:6 and
+ * to no joint row.  One inward pass in O(n_dof): no Jacobian is formed.  The wrench rows of bodies of box / sphere actors are
+ * IGNORED (by select: a NaN or Inf there does not reach tau).  wrench_dev and tau_dev must not overlap.
+ * NOT in either: no drives, no limits, no contact forces - the contact-force tensor is not a wrench, and nothing here reads it.
+ * Launches on the context's stream only - no allocation, no copy, no synchronise: both can sit in a captured graph.
+ * MPPI_EINVAL: a null acc_dev / wrench_dev / tau_dev, a range outside [0, n_rb), unknown bits in terms.  MPPI_EUNSUPPORTED
+ * (mppi_last_error says which): a fixed-base robot or fixed-base forest (use mppi_sim_link_acceleration / mppi_sim_wrench_forces), a
+ * forest of several moving bases (n_extra_bases > 0), a kinematic tree whose launch table lacks the kernel.  Refused before any
+ * launch. */
+int mppi_sim_floating_link_acceleration(mppi_ctx_t *ctx, int rb_first, int rb_count, const float *vd_dev /* [K][6 + n_dof] or NULL */, int terms,
+                                        float *acc_dev /* [K][rb_count][6] */);
+int mppi_sim_floating_wrench_forces(mppi_ctx_t *ctx, int rb_first, int rb_count, const float *wrench_dev /* [K][rb_count][6] */,
+                                    float *tau_dev /* [K][6 + n_dof] */);
 int mppi_sim_accumulate_cost(mppi_ctx_t *ctx, int t, const float *cost_dev); /* S += gamma^t c      */
 int mppi_sim_finish(mppi_ctx_t *ctx);                      /* S += control cost                     */
 /* The same horizon in TWO launches for host-side costs that are functions of the state tensors (mppi_isaac.py:57-69 evaluates

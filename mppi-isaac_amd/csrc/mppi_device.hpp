@@ -1743,14 +1743,19 @@ MPPI_HD void floating_forward_dynamics(M &m0, const Pose<T> &P, const V3 *d, con
     forward_dynamics_pass<true, T>(m0, P, d, v, tau, terms, vd);
 }
 
-// ---- link accelerations and the joint forces of link wrenches of one env of a FIXED-base robot ----
-// (mppi_sim_link_acceleration / mppi_sim_wrench_forces: the two halves of the Newton-Euler recursion of inverse_dynamics, each
-// on its own - the outward half without the inertias, the inward half without the motion)
+// ---- link accelerations and the joint forces of link wrenches of one env: of a FIXED-base robot (mppi_sim_link_acceleration /
+// ---- mppi_sim_wrench_forces) and of a robot with ONE moving base (mppi_sim_floating_link_acceleration / mppi_sim_floating_wrench_forces)
+// (the two halves of the Newton-Euler recursion of inverse_dynamics, each on its own - the outward half without the inertias, the
+// inward half without the motion)
 
 // Angular velocity, angular acceleration and the acceleration of the body ORIGIN of every body, world axes
 template <class T>
 struct BodyMotion {
     V3 w[T::NB ? T::NB : 1], wd[T::NB ? T::NB : 1], ao[T::NB ? T::NB : 1];
+};
+// ... and of a moving base, carried beside it (the fixed front has none: its BodyMotion stays as it was)
+struct BaseMotion {
+    V3 w, wd, ao;
 };
 
 // The outward pass of inverse_dynamics without gravity and without the inertias: B of the motion (qd, qdd) at the body poses P.
@@ -1758,19 +1763,32 @@ struct BodyMotion {
 // the angular acceleration, a prismatic one 2 w x (qd a) + qdd a to the origin's.  The accelerations are linear in qdd and
 // quadratic in qd: a part that is not asked for (qdd null, kIdVelocity not in terms) is left out by zeroing its input, so the parts
 // of separate calls are the very sums of one call, and with nothing asked for every product has a zero factor.
-template <class T>
-MPPI_HD void link_accelerations(const Pose<T> &P, const V3 *d, const float *qd, const float *qdd, int terms, BodyMotion<T> &B) {
-    constexpr int NB = T::NB;
+//
+// MOVING = true (floating_link_accelerations): qd and qdd are [6 + NB] in the generalised velocity v = (root linvel, root angvel, qd)
+// of floating_link_jacobian and its time derivative.  The bodies next to the base start from the base's motion Bb - w_b = v[3:6]
+// (zero without kIdVelocity), w_b' = v'[3:6], a_b = v'[0:3], the start of inverse_dynamics_pass<true> with a0 = 0 - and ride on it
+// through d[i] = p_i - p_base.  The linear velocity of the base enters nowhere, and neither does its position.
+template <bool MOVING, class T>
+MPPI_HD void link_accelerations_pass(const Pose<T> &P, const V3 *d, const float *qd, const float *qdd, int terms, BodyMotion<T> &B, BaseMotion &Bb) {
+    constexpr int NB = T::NB, C0 = MOVING ? 6 : 0;
     const bool with_v = (terms & kIdVelocity) != 0;
     const V3 zero = {0.f, 0.f, 0.f};
+    if constexpr (MOVING) {
+        Bb.w = with_v ? V3{qd[3], qd[4], qd[5]} : zero;
+        Bb.wd = qdd != nullptr ? V3{qdd[3], qdd[4], qdd[5]} : zero;
+        Bb.ao = qdd != nullptr ? V3{qdd[0], qdd[1], qdd[2]} : zero;
+    }
     static_for<0, NB>([&](auto ic) MPPI_LAMBDA {
         constexpr int i = ic;
         constexpr int par = T::par[i];
         constexpr int pj = par < 0 ? 0 : par;
         const V3 az = {P.R[i].a[2], P.R[i].a[5], P.R[i].a[8]};
         const bool rev = P.jt[i] == 0;
-        const float vi = with_v ? qd[i] : 0.f, ai = qdd != nullptr ? qdd[i] : 0.f;
-        const V3 wp = par < 0 ? zero : B.w[pj], wdp = par < 0 ? zero : B.wd[pj], ap = par < 0 ? zero : B.ao[pj];
+        const float vi = with_v ? qd[C0 + i] : 0.f, ai = qdd != nullptr ? qdd[C0 + i] : 0.f;
+        // (the fixed front reads the constant where the moving one reads the base's motion: a variable that merely holds zero would
+        // change the registers of the fixed kernels)
+        const V3 wp = par < 0 ? (MOVING ? Bb.w : zero) : B.w[pj], wdp = par < 0 ? (MOVING ? Bb.wd : zero) : B.wd[pj],
+                 ap = par < 0 ? (MOVING ? Bb.ao : zero) : B.ao[pj];
         const V3 sv = vi * az, sa = ai * az;
         V3 acc = ap + cross(wdp, d[i]) + cross(wp, cross(wp, d[i]));
         if (!rev) acc = acc + 2.f * cross(wp, sv) + sa;
@@ -1779,19 +1797,41 @@ MPPI_HD void link_accelerations(const Pose<T> &P, const V3 *d, const float *qd, 
         B.ao[i] = acc;
     });
 }
+template <class T>
+MPPI_HD void link_accelerations(const Pose<T> &P, const V3 *d, const float *qd, const float *qdd, int terms, BodyMotion<T> &B) {
+    BaseMotion none;  // (never touched by the fixed front)
+    link_accelerations_pass<false, T>(P, d, qd, qdd, terms, B, none);
+}
+// v [6 + NB] (rows 0-2, the linear velocity of the base, are not read), vd [6 + NB] or null
+template <class T>
+MPPI_HD void floating_link_accelerations(const Pose<T> &P, const V3 *d, const float *v, const float *vd, int terms, BodyMotion<T> &B, BaseMotion &Bb) {
+    link_accelerations_pass<true, T>(P, d, v, vd, terms, B, Bb);
+}
 
 // a [6] of robot link l from the motion B of the bodies: rows 0-2 the classical acceleration of the link frame origin,
 // a_body + wd x r + w x (w x r) with r = R_body link.p the link's offset on its body, rows 3-5 the angular acceleration - the time
 // derivative of what link_jacobian's J qd reports.  The link's body is a run-time (wave-uniform) index, resolved by a 0/1-weighted
 // blend as in link_pose.  l outside [0, nl) (the body of a box or sphere actor) and links welded to the fixed base: exact zeros.
-template <class T, class M>
-MPPI_HD void link_acceleration(M &m, const Pose<T> &P, const BodyMotion<T> &B, int l, float *a) {
+//
+// MOVING = true (floating_link_acceleration): the base is one more candidate of the blend (as Rb of link_jacobian_columns), so a link
+// welded to the base moves with it - a_b + w_b' x r + w_b x (w_b x r), w_b' with r = R_base link.p - and only the bodies that are no
+// robot link keep their exact zeros.
+template <bool MOVING, class T, class M>
+MPPI_HD void link_acceleration_of(M &m, const Pose<T> &P, const BodyMotion<T> &B, const BaseMotion &Bb, int l, float *a) {
     const bool robot = l >= 0 && l < m.nl;
     const int ll = robot ? l : 0;
     const int body = robot ? m.l[ll].body : -1;
     M3 Rb;
-    for (int j = 0; j < 9; j++) Rb.a[j] = 0.f;
     V3 w = {0.f, 0.f, 0.f}, wd = w, ao = w;
+    if constexpr (MOVING) {
+        const float sb = robot && body < 0 ? 1.f : 0.f;
+        for (int j = 0; j < 9; j++) Rb.a[j] = sb * P.Rb.a[j];
+        w = sb * Bb.w;
+        wd = sb * Bb.wd;
+        ao = sb * Bb.ao;
+    } else {
+        for (int j = 0; j < 9; j++) Rb.a[j] = 0.f;
+    }
     static_for<0, T::NB>([&](auto ic) MPPI_LAMBDA {
         constexpr int i = ic;
         const float s = body == i ? 1.f : 0.f;
@@ -1802,7 +1842,7 @@ MPPI_HD void link_acceleration(M &m, const Pose<T> &P, const BodyMotion<T> &B, i
     });
     const V3 r = mul(Rb, loadv(m.l[ll].p));
     const V3 lin = ao + cross(wd, r) + cross(w, cross(w, r));
-    const bool on = body >= 0;
+    const bool on = MOVING ? robot : body >= 0;
     a[0] = on ? lin.x : 0.f;
     a[1] = on ? lin.y : 0.f;
     a[2] = on ? lin.z : 0.f;
@@ -1810,17 +1850,34 @@ MPPI_HD void link_acceleration(M &m, const Pose<T> &P, const BodyMotion<T> &B, i
     a[4] = on ? wd.y : 0.f;
     a[5] = on ? wd.z : 0.f;
 }
+template <class T, class M>
+MPPI_HD void link_acceleration(M &m, const Pose<T> &P, const BodyMotion<T> &B, int l, float *a) {
+    const BaseMotion none = {};  // (never read by the fixed front)
+    link_acceleration_of<false, T>(m, P, B, none, l, a);
+}
+template <class T, class M>
+MPPI_HD void floating_link_acceleration(M &m, const Pose<T> &P, const BodyMotion<T> &B, const BaseMotion &Bb, int l, float *a) {
+    link_acceleration_of<true, T>(m, P, B, Bb, l, a);
+}
 
 // The wrench (f on the link, n about the link frame origin; world axes) on robot link l, moved to the origin of the link's body and
 // added to that body's sums: F_i += f, N_i += n + r x f, r = R_body link.p.  l outside [0, nl) and links welded to the fixed base
 // take no part - by select, never by a product with zero: a NaN or Inf in such a row does not reach any sum.
-template <class T, class M>
-MPPI_HD void gather_link_wrench(M &m, const Pose<T> &P, int l, V3 f, V3 n, V3 *F, V3 *N) {
+//
+// MOVING = true (gather_floating_link_wrench): the wrench on a link welded to the base goes to the base's own sums (Fb, Nb about the
+// base origin, r = R_base link.p), by the same select; only the bodies that are no robot link take no part.
+template <bool MOVING, class T, class M>
+MPPI_HD void gather_link_wrench_on(M &m, const Pose<T> &P, int l, V3 f, V3 n, V3 *F, V3 *N, V3 &Fb, V3 &Nb) {
     const bool robot = l >= 0 && l < m.nl;
     const int ll = robot ? l : 0;
     const int body = robot ? m.l[ll].body : -1;
     M3 Rb;
-    for (int j = 0; j < 9; j++) Rb.a[j] = 0.f;
+    if constexpr (MOVING) {
+        const float sb = robot && body < 0 ? 1.f : 0.f;
+        for (int j = 0; j < 9; j++) Rb.a[j] = sb * P.Rb.a[j];
+    } else {
+        for (int j = 0; j < 9; j++) Rb.a[j] = 0.f;
+    }
     static_for<0, T::NB>([&](auto ic) MPPI_LAMBDA {
         constexpr int i = ic;
         const float s = body == i ? 1.f : 0.f;
@@ -1835,25 +1892,61 @@ MPPI_HD void gather_link_wrench(M &m, const Pose<T> &P, int l, V3 f, V3 n, V3 *F
         F[i] = {on ? Fi.x : F[i].x, on ? Fi.y : F[i].y, on ? Fi.z : F[i].z};
         N[i] = {on ? Ni.x : N[i].x, on ? Ni.y : N[i].y, on ? Ni.z : N[i].z};
     });
+    if constexpr (MOVING) {
+        const bool on = robot && body < 0;
+        const V3 Fi = Fb + f, Ni = Nb + nb;
+        Fb = {on ? Fi.x : Fb.x, on ? Fi.y : Fb.y, on ? Fi.z : Fb.z};
+        Nb = {on ? Ni.x : Nb.x, on ? Ni.y : Nb.y, on ? Ni.z : Nb.z};
+    }
+}
+template <class T, class M>
+MPPI_HD void gather_link_wrench(M &m, const Pose<T> &P, int l, V3 f, V3 n, V3 *F, V3 *N) {
+    V3 Fb, Nb;  // (never touched by the fixed front)
+    gather_link_wrench_on<false, T>(m, P, l, f, n, F, N, Fb, Nb);
+}
+template <class T, class M>
+MPPI_HD void gather_floating_link_wrench(M &m, const Pose<T> &P, int l, V3 f, V3 n, V3 *F, V3 *N, V3 &Fb, V3 &Nb) {
+    gather_link_wrench_on<true, T>(m, P, l, f, n, F, N, Fb, Nb);
 }
 
 // tau [NB] = sum over the links of J_link^T (f, n) from the wrenches gathered on the bodies (F_i, N_i about p_i; gather_link_wrench):
 // the inward pass of inverse_dynamics.  tau_i = a_i . N_i (revolute) or a_i . F_i (prismatic), then the body's sums go to the
 // parent's origin - the same force, its moment moved by d[i] only.  No Jacobian is formed, nothing is a difference of world
 // positions.  F and N are used up.
-template <class T>
-MPPI_HD void wrench_joint_forces(const Pose<T> &P, const V3 *d, V3 *F, V3 *N, float *tau) {
+//
+// MOVING = true (floating_wrench_joint_forces): tau [6 + NB], the joints at 6 + i; the bodies next to the base hand F_i and
+// N_i + d_i x F_i on to the base origin, where the wrenches on the base's own links wait (Fb, Nb); rows 0:3 are the total force on the
+// base, rows 3:6 the total moment about the base origin.
+template <bool MOVING, class T>
+MPPI_HD void wrench_joint_forces_pass(const Pose<T> &P, const V3 *d, V3 *F, V3 *N, V3 Fb, V3 Nb, float *tau) {
+    constexpr int C0 = MOVING ? 6 : 0;
     static_rfor<0, T::NB>([&](auto ic) MPPI_LAMBDA {
         constexpr int i = ic;
         constexpr int par = T::par[i];
         const V3 az = {P.R[i].a[2], P.R[i].a[5], P.R[i].a[8]};
-        tau[i] = P.jt[i] == 0 ? dot(az, N[i]) : dot(az, F[i]);
+        tau[C0 + i] = P.jt[i] == 0 ? dot(az, N[i]) : dot(az, F[i]);
         if constexpr (par >= 0) {
             constexpr int pj = par < 0 ? 0 : par;
             N[pj] = N[pj] + N[i] + cross(d[i], F[i]);
             F[pj] = F[pj] + F[i];
+        } else if constexpr (MOVING) {
+            Nb = Nb + N[i] + cross(d[i], F[i]);
+            Fb = Fb + F[i];
         }
     });
+    if constexpr (MOVING) {
+        tau[0] = Fb.x; tau[1] = Fb.y; tau[2] = Fb.z;
+        tau[3] = Nb.x; tau[4] = Nb.y; tau[5] = Nb.z;
+    }
+}
+template <class T>
+MPPI_HD void wrench_joint_forces(const Pose<T> &P, const V3 *d, V3 *F, V3 *N, float *tau) {
+    const V3 zero = {0.f, 0.f, 0.f};
+    wrench_joint_forces_pass<false, T>(P, d, F, N, zero, zero, tau);
+}
+template <class T>
+MPPI_HD void floating_wrench_joint_forces(const Pose<T> &P, const V3 *d, V3 *F, V3 *N, V3 Fb, V3 Nb, float *tau) {
+    wrench_joint_forces_pass<true, T>(P, d, F, N, Fb, Nb, tau);
 }
 
 }  // namespace mppi

@@ -1498,6 +1498,34 @@ int mppi_sim_floating_forward_dynamics(mppi_ctx_t *c, const float *tau_dev, int 
     e->sim_floating_forward_dynamics(c, tau_dev, terms, vd_dev);
     return launch_check();
 }
+/* how the links of a robot with a moving base accelerate, a = J v' + Jdot v in the same generalised velocity: launches on the
+ * context's stream, no allocation, no copy, no synchronise (include/mppi_hip.h) */
+int mppi_sim_floating_link_acceleration(mppi_ctx_t *c, int rb_first, int rb_count, const float *vd_dev, int terms, float *acc_dev) {
+    CTX_TRY(c);
+    if (!acc_dev) return fail(MPPI_EINVAL, "mppi_sim_floating_link_acceleration: null output");
+    if (int rc = rb_range_check(c, "mppi_sim_floating_link_acceleration", rb_first, rb_count)) return rc;
+    if (terms & ~MPPI_ID_VELOCITY)
+        return fail(MPPI_EINVAL, "mppi_sim_floating_link_acceleration: unknown bits in terms = " + std::to_string(terms) +
+                                     " (MPPI_ID_VELOCITY only: gravity has no part in a kinematic quantity)");
+    const TopoEntry *e = nullptr;
+    if (int rc = floating_entry(c, "mppi_sim_floating_link_acceleration", "mppi_sim_link_acceleration", e)) return rc;
+    if (!e->sim_floating_link_acceleration) return fail(MPPI_EUNSUPPORTED, "mppi_sim_floating_link_acceleration: not available for this kinematic tree");
+    e->sim_floating_link_acceleration(c, rb_first, rb_count, vd_dev, terms, acc_dev);
+    return launch_check();
+}
+/* what wrenches on links ask of the base and the joints of a robot with a moving base, tau = sum J^T w: one launch on the context's
+ * stream, no allocation, no copy, no synchronise (include/mppi_hip.h) */
+int mppi_sim_floating_wrench_forces(mppi_ctx_t *c, int rb_first, int rb_count, const float *wrench_dev, float *tau_dev) {
+    CTX_TRY(c);
+    if (!wrench_dev) return fail(MPPI_EINVAL, "mppi_sim_floating_wrench_forces: null wrenches");
+    if (!tau_dev) return fail(MPPI_EINVAL, "mppi_sim_floating_wrench_forces: null output");
+    if (int rc = rb_range_check(c, "mppi_sim_floating_wrench_forces", rb_first, rb_count)) return rc;
+    const TopoEntry *e = nullptr;
+    if (int rc = floating_entry(c, "mppi_sim_floating_wrench_forces", "mppi_sim_wrench_forces", e)) return rc;
+    if (!e->sim_floating_wrench_forces) return fail(MPPI_EUNSUPPORTED, "mppi_sim_floating_wrench_forces: not available for this kinematic tree");
+    e->sim_floating_wrench_forces(c, rb_first, rb_count, wrench_dev, tau_dev);
+    return launch_check();
+}
 int mppi_sim_accumulate_cost(mppi_ctx_t *c, int t, const float *cost_dev) {
     CTX_TRY(c);
     if (!cost_dev) return fail(MPPI_EINVAL, "null cost");

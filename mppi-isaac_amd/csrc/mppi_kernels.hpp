@@ -2109,6 +2109,96 @@ __global__ __launch_bounds__(kWave) void k_sim_floating_forward_dynamics(const D
     __syncthreads();
     store_staged_rows<kLen>(s_row, n_rows, out + (size_t)k0 * kLen, kLen);
 }
+// ---- link accelerations and the forces of link wrenches for a robot with a MOVING base (mppi_sim_floating_link_acceleration /
+// ---- mppi_sim_floating_wrench_forces): k_sim_link_acceleration and k_sim_wrench_forces in the generalised velocity above ----
+// out [K][rb_count][6] = J v' (vd_ [K][6 + n], null: left out) + Jdot v (with kIdVelocity) of rigid bodies rb_first .. rb_first + rb_count - 1
+// with the J of k_sim_floating_jacobian (floating_link_accelerations / floating_link_acceleration, mppi_device.hpp; links welded to
+// the base move with it, bodies that are no robot link get zero rows).  Every env reads ITS OWN base rows: the pose as sim_env_pose
+// does, the twist - columns 7:13 - here.  The v' rows come in through the tile at the stride of 6 + n floats; the outward pass runs
+// once per env; then the tile is six floats per lane and goes out one body per staging pass.  Every barrier is reached by the
+// whole wavefront (vd_, rb_count are uniform); rows past K - 1 of the last wavefront are neither loaded nor stored.
+template <class T>
+__global__ __launch_bounds__(kWave) void k_sim_floating_link_acceleration(const DevModel *__restrict__ m, int K, const float *__restrict__ x0_root,
+                                                                          const float *__restrict__ q_, const float *__restrict__ qd_,
+                                                                          const float *__restrict__ base_, const float *__restrict__ vd_, int terms,
+                                                                          int rb_first, int rb_count, float *__restrict__ out) {
+    constexpr int NB = T::NB, kIn = 6 + NB, kInStride = staged_stride(kIn), kLen = 6, kStride = staged_stride(kLen);
+    __shared__ float s_row[kWave * (kInStride > kStride ? kInStride : kStride)];
+    CModel &M = *(CModel *)m;
+    const int k0 = blockIdx.x * kWave, k = k0 + threadIdx.x;
+    const int n_rows = K - k0 < kWave ? K - k0 : kWave;
+    if (vd_ != nullptr) {
+        load_staged_rows<kIn>(s_row, n_rows, vd_ + (size_t)k0 * kIn, kIn);
+        __syncthreads();
+    }
+    Pose<T> P;
+    BodyMotion<T> B;
+    BaseMotion Bb;
+    if (k < K) {
+        V3 d[NB ? NB : 1];
+        float v[kIn], vd[kIn];
+        sim_env_pose<T>(M, K, k, x0_root, q_, base_, P, d);
+        for (int j = 0; j < 6; j++) v[j] = base_[(size_t)(7 + j) * K + k];
+        static_for<0, NB>([&](auto ic) {
+            constexpr int i = ic;
+            v[6 + i] = qd_[(size_t)i * K + k];
+        });
+        static_for<0, kIn>([&](auto jc) {
+            constexpr int j = jc;
+            vd[j] = vd_ != nullptr ? s_row[threadIdx.x * kInStride + j] : 0.f;
+        });
+        floating_link_accelerations<T>(P, d, v, vd, terms, B, Bb);  // (v' left out: zeros - the same sums, as in k_sim_link_acceleration)
+    }
+    __syncthreads();  // the v' rows are read: the tile changes its stride
+    for (int j = 0; j < rb_count; j++) {
+        if (k < K) floating_link_acceleration<T>(M, P, B, Bb, rb_first + j - M.robot_first_rb, s_row + threadIdx.x * kStride);
+        __syncthreads();
+        store_staged_rows<kLen>(s_row, n_rows, out + ((size_t)k0 * rb_count + j) * kLen, (size_t)rb_count * kLen);
+        __syncthreads();
+    }
+}
+// tau [K][6 + n] = sum over rigid bodies rb_first .. rb_first + rb_count - 1 of J_b^T w[k][b] (w [K][rb_count][6]: force on the link,
+// moment about the link frame origin) with the J of k_sim_floating_jacobian (gather_floating_link_wrench / floating_wrench_joint_forces,
+// mppi_device.hpp): rows 0:3 the total force on the base, rows 3:6 the total moment about the base origin, then the joints.  The
+// wrenches on links welded to the base go to the base's sums; the rows of bodies that are no robot link are ignored by select.
+// Staged as k_sim_wrench_forces: six floats per lane per body in, 6 + n floats per lane out, a uniform loop count at every barrier.
+template <class T>
+__global__ __launch_bounds__(kWave) void k_sim_floating_wrench_forces(const DevModel *__restrict__ m, int K, const float *__restrict__ x0_root,
+                                                                      const float *__restrict__ q_, const float *__restrict__ base_, int rb_first,
+                                                                      int rb_count, const float *__restrict__ w_, float *__restrict__ out) {
+    constexpr int NB = T::NB, kLen = 6 + NB, kStride = staged_stride(kLen), kIn = 6, kInStride = staged_stride(kIn);
+    __shared__ float s_row[kWave * (kInStride > kStride ? kInStride : kStride)];
+    CModel &M = *(CModel *)m;
+    const int k0 = blockIdx.x * kWave, k = k0 + threadIdx.x;
+    const int n_rows = K - k0 < kWave ? K - k0 : kWave;
+    Pose<T> P;
+    V3 d[NB ? NB : 1], F[NB ? NB : 1], N[NB ? NB : 1];
+    V3 Fb = {0.f, 0.f, 0.f}, Nb = Fb;
+    if (k < K) sim_env_pose<T>(M, K, k, x0_root, q_, base_, P, d);
+    static_for<0, NB>([&](auto ic) {
+        constexpr int i = ic;
+        F[i] = N[i] = V3{0.f, 0.f, 0.f};
+    });
+    for (int j = 0; j < rb_count; j++) {
+        load_staged_rows<kIn>(s_row, n_rows, w_ + ((size_t)k0 * rb_count + j) * kIn, (size_t)rb_count * kIn);
+        __syncthreads();
+        if (k < K) {
+            const float *w = s_row + threadIdx.x * kInStride;
+            gather_floating_link_wrench<T>(M, P, rb_first + j - M.robot_first_rb, V3{w[0], w[1], w[2]}, V3{w[3], w[4], w[5]}, F, N, Fb, Nb);
+        }
+        __syncthreads();
+    }
+    if (k < K) {
+        float tau[kLen];
+        floating_wrench_joint_forces<T>(P, d, F, N, Fb, Nb, tau);
+        static_for<0, kLen>([&](auto jc) {
+            constexpr int j = jc;
+            s_row[threadIdx.x * kStride + j] = tau[j];
+        });
+    }
+    __syncthreads();
+    store_staged_rows<kLen>(s_row, n_rows, out + (size_t)k0 * kLen, kLen);
+}
 
 // Parity / debug entry (mppi_eval_cost): the cost program of the context evaluated by the interpreter the rollout kernels run
 // (program_cost_with, mppi_device.hpp) on CALLER-GIVEN simulator answers - reference-layout rows of n envs - instead of the
@@ -2311,6 +2401,11 @@ struct TopoEntry {
     void (*sim_floating_forward_dynamics)(mppi_ctx *, const float *, int, float *);  // mppi_sim_floating_forward_dynamics
     hipError_t (*raise_lds)(size_t, size_t);
     size_t (*static_lds)();  // largest static __shared__ footprint among the contact-scene kernels (counts against the 160 KiB too)
+    // the two halves of the Newton-Euler recursion for ONE moving base (filled by the contact-scene unit, as the four sim_floating_*
+    // entries above; at the end of the row): mppi_sim_floating_link_acceleration
+    void (*sim_floating_link_acceleration)(mppi_ctx *, int, int, const float *, int, float *);
+    // mppi_sim_floating_wrench_forces
+    void (*sim_floating_wrench_forces)(mppi_ctx *, int, int, const float *, float *);
 };
 }  // namespace mppi
 
@@ -2432,6 +2527,16 @@ template <class T>
 void launch_sim_floating_forward_dynamics_t(mppi_ctx *c, const float *tau, int terms, float *out) {
     hipLaunchKernelGGL(k_sim_floating_forward_dynamics<T>, dim3(c->n_waves), dim3(kWave), 0, c->stream, c->d_model, c->K, c->d_x0_root, c->d_q, c->d_qd,
                        c->d_base, tau, terms, out);
+}
+template <class T>
+void launch_sim_floating_link_acceleration_t(mppi_ctx *c, int rb_first, int rb_count, const float *vd, int terms, float *out) {
+    hipLaunchKernelGGL(k_sim_floating_link_acceleration<T>, dim3(c->n_waves), dim3(kWave), 0, c->stream, c->d_model, c->K, c->d_x0_root, c->d_q, c->d_qd,
+                       c->d_base, vd, terms, rb_first, rb_count, out);
+}
+template <class T>
+void launch_sim_floating_wrench_forces_t(mppi_ctx *c, int rb_first, int rb_count, const float *w, float *out) {
+    hipLaunchKernelGGL(k_sim_floating_wrench_forces<T>, dim3(c->n_waves), dim3(kWave), 0, c->stream, c->d_model, c->K, c->d_x0_root, c->d_q, c->d_base,
+                       rb_first, rb_count, w, out);
 }
 template <class T>
 hipError_t raise_lds_limit(size_t lane_bytes, size_t quad_bytes) {  // lane_bytes == 0: the one-lane kernels are not used
@@ -2593,11 +2698,13 @@ void fill_topo_entry_scene(TopoEntry &e) {
     e.materialise_scene = &launch_materialise_scene_t<T>;
     e.raise_lds = &raise_lds_limit<T>;
     e.static_lds = &static_lds_bytes_scene<T>;
-    if constexpr (T::NBASE == 1) {  // (a forest of several moving bases is refused by the four entries: nothing to launch)
+    if constexpr (T::NBASE == 1) {  // (a forest of several moving bases is refused by the six entries: nothing to launch)
         e.sim_floating_jacobian = &launch_sim_floating_jacobian_t<T>;
         e.sim_floating_mass_matrix = &launch_sim_floating_mass_matrix_t<T>;
         e.sim_floating_inverse_dynamics = &launch_sim_floating_inverse_dynamics_t<T>;
         e.sim_floating_forward_dynamics = &launch_sim_floating_forward_dynamics_t<T>;
+        e.sim_floating_link_acceleration = &launch_sim_floating_link_acceleration_t<T>;
+        e.sim_floating_wrench_forces = &launch_sim_floating_wrench_forces_t<T>;
     }
 }
 

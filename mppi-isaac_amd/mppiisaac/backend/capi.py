@@ -164,6 +164,8 @@ _SIGNATURES = {
     "mppi_sim_floating_mass_matrix": (C.c_int, [_vp, _vp]),
     "mppi_sim_floating_inverse_dynamics": (C.c_int, [_vp, _vp, C.c_int, _vp]),
     "mppi_sim_floating_forward_dynamics": (C.c_int, [_vp, _vp, C.c_int, _vp]),
+    "mppi_sim_floating_link_acceleration": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp]),
+    "mppi_sim_floating_wrench_forces": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
     "mppi_sim_accumulate_cost": (C.c_int, [_vp, C.c_int, _vp]),
     "mppi_sim_finish": (C.c_int, [_vp]),
     "mppi_rollout_trajectory": (C.c_int, [_vp]),

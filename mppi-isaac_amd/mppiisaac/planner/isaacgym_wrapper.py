@@ -653,6 +653,7 @@ class IsaacGymWrapper:
         self._floating_jacobians, self._floating_mass_matrix = {}, None   # acquire_floating_*_tensor: filled by refresh_floating_*()
         self._floating_bias_force = None                # acquire_floating_bias_force_tensor: filled by refresh_floating_bias_force_tensors()
         self._floating_free_acceleration = None         # acquire_floating_free_acceleration_tensor: filled by refresh_floating_free_acceleration_tensors()
+        self._floating_link_bias_acceleration = {}      # acquire_floating_link_bias_acceleration_tensor: filled by refresh_floating_link_bias_acceleration_tensors()
         self._visualize_link_present = sc.viz_link_index() >= 0
         self.visualize_link_buffer = []
         if self._visualize_link_present:
@@ -1162,6 +1163,86 @@ class IsaacGymWrapper:
             self._physics_call(self._lib.mppi_sim_floating_forward_dynamics, _dev_ptr(units[c]), 0, _dev_ptr(cols[c]), what=self._FFD_WHAT)
         low = torch.tril(cols.permute(1, 2, 0))      # [K, row, column]
         return low + torch.tril(low, -1).transpose(1, 2)
+
+    # ------------------------------------------------------------------ link accelerations and wrench forces of a robot with a moving base
+    # a = J v' + Jdot v of a link and tau = sum J^T w of wrenches on links, in the same generalised velocity and with the J of the
+    # floating Jacobians (mppi_sim_floating_link_acceleration / mppi_sim_floating_wrench_forces; no Jacobian is formed).  tau is
+    # [K, 6 + n_dof]: rows 0:3 the total force on the base, rows 3:6 the total moment about the base origin, then the joints - the
+    # J^T f to ADD to a tau given to floating_forward_dynamics.  Links welded to the base move with it and load rows 0:6 only.  A
+    # fixed-base robot raises NotImplementedError with the library's text: link_accelerations / joint_forces_from_wrenches below
+    # are the ones to use.
+    _FLA_WHAT = "moving-base link accelerations and wrench forces"
+
+    def _vd_rows(self, vd):
+        K, n = self.num_envs, 6 + self.scene.n_dof
+        if vd is None:
+            return None
+        vd = torch.as_tensor(vd, dtype=torch.float32, device=self.device)
+        if tuple(vd.shape) == (n,):
+            vd = vd.expand(K, n)
+        elif tuple(vd.shape) != (K, n):
+            raise ValueError(f"vd has shape {tuple(vd.shape)}: expected [{n}] or [{K}, {n}]")
+        return vd.contiguous()
+
+    def _floating_link_acceleration_call(self, first, count, vd, velocity):
+        self._live_envs_only(self._FLA_WHAT)
+        vd = self._vd_rows(vd)
+        out = torch.empty((self.num_envs, count, 6), dtype=torch.float32, device=self.device)
+        self._physics_call(self._lib.mppi_sim_floating_link_acceleration, first, count, _dev_ptr(vd), capi.ID_VELOCITY if velocity else 0,
+                           _dev_ptr(out), what=self._FLA_WHAT)
+        return out
+
+    def floating_link_accelerations(self, actor_name: str, vd=None, velocity=True):
+        """a fresh [K, L, 6] tensor J v' (vd None: left out) + Jdot v (velocity) of every rigid body of the actor at the envs' own
+        base poses, twists, joint positions and rates.  vd: [6 + n_dof], the same acceleration for every env, or [K, 6 + n_dof]:
+        (acceleration of the root frame origin, angular acceleration, qdd)."""
+        return self._floating_link_acceleration_call(*self._actor_rb_range(actor_name), vd, velocity)
+
+    def get_actor_link_floating_acceleration_by_name(self, actor_name: str, link_name: str, vd=None, velocity=True):
+        """a fresh [K, 6] acceleration of one link (a one-body launch): the counterpart of get_actor_link_floating_jacobian_by_name"""
+        rb = self.scene.rigid_body_index(actor_name, link_name)
+        return self._floating_link_acceleration_call(rb, 1, vd, velocity)[:, 0, :]
+
+    def acquire_floating_link_bias_acceleration_tensor(self, actor_name: str):
+        """[K, L, 6]: Jdot v of every rigid body of the actor - the velocity-product acceleration of the task-space equation
+        xdd = J v' + Jdot v.  Zero until refresh_floating_link_bias_acceleration_tensors()."""
+        self._live_envs_only(self._FLA_WHAT)
+        if actor_name not in self._floating_link_bias_acceleration:
+            first, count = self._actor_rb_range(actor_name)
+            t = torch.zeros((self.num_envs, count, 6), dtype=torch.float32, device=self.device)
+            self._floating_link_bias_acceleration[actor_name] = (first, count, t)
+        return self._floating_link_bias_acceleration[actor_name][2]
+
+    def refresh_floating_link_bias_acceleration_tensors(self) -> None:
+        self._live_envs_only(self._FLA_WHAT)
+        for first, count, t in self._floating_link_bias_acceleration.values():
+            self._physics_call(self._lib.mppi_sim_floating_link_acceleration, first, count, None, capi.ID_VELOCITY, _dev_ptr(t),
+                               what=self._FLA_WHAT)
+
+    def _floating_wrench_forces_call(self, first, count, wrenches, one, many):
+        self._live_envs_only(self._FLA_WHAT)
+        K = self.num_envs
+        w = torch.as_tensor(wrenches, dtype=torch.float32, device=self.device)
+        if tuple(w.shape) == one:
+            w = w.expand(K, *one)
+        elif tuple(w.shape) != many:
+            raise ValueError(f"wrenches have shape {tuple(w.shape)}: expected {list(one)} or {list(many)}")
+        w = w.contiguous()
+        out = torch.empty((K, 6 + self.scene.n_dof), dtype=torch.float32, device=self.device)
+        self._physics_call(self._lib.mppi_sim_floating_wrench_forces, first, count, _dev_ptr(w), _dev_ptr(out), what=self._FLA_WHAT)
+        return out
+
+    def floating_forces_from_wrenches(self, actor_name: str, wrenches):
+        """a fresh [K, 6 + n_dof] tensor sum_b J_b^T w_b: the base force, base moment and joint forces that do the work of the wrenches
+        on the actor's rigid bodies (ADD them to a tau given to floating_forward_dynamics, SUBTRACT them from what
+        floating_inverse_dynamics returns).  wrenches: [L, 6], the same for every env, or [K, L, 6]."""
+        first, count = self._actor_rb_range(actor_name)
+        return self._floating_wrench_forces_call(first, count, wrenches, (count, 6), (self.num_envs, count, 6))
+
+    def floating_forces_from_link_wrench(self, actor_name: str, link_name: str, wrench):
+        """a fresh [K, 6 + n_dof] tensor J_link^T w of one wrench on one link (a one-body launch).  wrench: [6] or [K, 6]."""
+        rb = self.scene.rigid_body_index(actor_name, link_name)
+        return self._floating_wrench_forces_call(rb, 1, wrench, (6,), (self.num_envs, 6))
 
     # ------------------------------------------------------------------ inverse dynamics and bias forces
     # What joint forces a motion takes: tau = M(q) qdd + C(q, qd) qd + g(q) of every env at its current joint positions and rates
