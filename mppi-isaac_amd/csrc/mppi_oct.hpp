@@ -392,9 +392,11 @@ __device__ __forceinline__ void ooutward_fused_check(OF W, OF ap, OF cb, OF S, O
 // CHECK: the drive-limit test of quad_step rides in the wait slots of the outward pass (ooutward_fused_check): tt[i] = tau_exp[i] -
 // kdh[i] qdd[i] and excess = max_i(|tt[i]| - effort_i) come back with the accelerations
 // JV: qd is an array of JOINT VECTORS (OctAbaJv below; all-revolute trees) - everything else as above
-template <class T, bool CHECK = false, bool JV = false, class BP, class M, int JT>
-__device__ __forceinline__ void oct_aba(M &m, BP bodies, const OctLane &ol, const QPose<T, JT> &P, const OF *qd, const OF *tau_exp, const OF *kdh, OF *qdd,
-                                        JointLimits *lim, OF *tt = nullptr, OF *excess_out = nullptr) {
+// a0: the acceleration the outward pass starts from (oct_base_accel: gravity as a fictitious acceleration -g of the base) - a
+// constant of the launch that the caller forms; the solve itself reads nothing of the model but the body blocks
+template <class T, bool CHECK = false, bool JV = false, class BP, int JT>
+__device__ __forceinline__ void oct_aba(BP bodies, const OctLane &ol, const QPose<T, JT> &P, const OF *qd, const OF *tau_exp, const OF *kdh, OF *qdd,
+                                        JointLimits *lim, OF a0, OF *tt = nullptr, OF *excess_out = nullptr) {
     constexpr int NB = T::NB;
     OF v[NB], w[NB], S[NB], cb[NB], W[NB], kk[NB], pacc[NB];
     OAI acc[NB];
@@ -463,10 +465,12 @@ __device__ __forceinline__ void oct_aba(M &m, BP bodies, const OctLane &ol, cons
             }
         }
     });
-    // pass 3: accelerations, root to leaves.  Gravity = fictitious base acceleration -g (linear lanes)
+    // pass 3: accelerations, root to leaves, from the base's a0.  The passes stay two scheduling regions, as they were while the
+    // gravity test stood between them (no instruction is issued for the barrier): scheduled as one region the substep of a
+    // nine-body tree moves ~100 values through the AGPR file (listing: 1223 -> 1286 instructions; with the barrier 1199), and
+    // the panda's gets seven more wait states than it has with it
+    __builtin_amdgcn_sched_barrier(0);
     OF a[NB];
-    OF a0 = zero;
-    if (m.gravity_on) a0 = ol.lin * qsel(-m.g[0], -m.g[1], -m.g[2]);
     OF excess = -INFINITY;
     static_for<0, NB>([&](auto ic) MPPI_LAMBDA {
         constexpr int i = ic;
@@ -501,6 +505,13 @@ __device__ __forceinline__ MPPI_LDS_AS DevBody *oct_lin_place(MPPI_LDS_AS void *
     const unsigned r = (unsigned)(unsigned long)raw, b = (unsigned)(unsigned long)model_bodies;
     return (MPPI_LDS_AS DevBody *)(unsigned long)(r + ((b + 128u - r) & 255u));
 }
+// Gravity = fictitious acceleration -g of the base (linear lanes), zero without gravity: where the outward pass of oct_aba starts
+template <class M>
+__device__ __forceinline__ OF oct_base_accel(M &m, const OctLane &ol) {
+    OF a0 = 0.f;
+    if (m.gravity_on) a0 = ol.lin * qsel(-m.g[0], -m.g[1], -m.g[2]);
+    return a0;
+}
 // the solve policy of quad_step / quad_rollout (mppi_quad.hpp QuadAba) for the octet layout
 struct OctAba {
     OctBodies bodies;
@@ -509,13 +520,13 @@ struct OctAba {
     static constexpr bool kJointVectors = false;
     template <class T, class M, int JT>
     __device__ __forceinline__ void aba(M &m, const QPose<T, JT> &P, const QF *qd, const QF *tau_exp, const QF *kdh, QF *qdd, JointLimits *lim) const {
-        oct_aba<T>(m, bodies, ol, P, qd, tau_exp, kdh, qdd, lim);
+        oct_aba<T>(bodies, ol, P, qd, tau_exp, kdh, qdd, lim, oct_base_accel(m, ol));
     }
     // ... and the drive-limit test of quad_step with it: tt[i] = tau_exp[i] - kdh[i] qdd[i], excess = max_i(|tt[i]| - effort_i)
     template <class T, class M, int JT>
     __device__ __forceinline__ void aba_checked(M &m, const QPose<T, JT> &P, const QF *qd, const QF *tau_exp, const QF *kdh, QF *qdd, JointLimits *lim,
                                                 QF *tt, QF &excess) const {
-        oct_aba<T, true>(m, bodies, ol, P, qd, tau_exp, kdh, qdd, lim, tt, &excess);
+        oct_aba<T, true>(bodies, ol, P, qd, tau_exp, kdh, qdd, lim, oct_base_accel(m, ol), tt, &excess);
     }
 };
 
@@ -553,10 +564,24 @@ struct OctAbaJv : OctAba {
     OF lo[NV], hi[NV], vmax[NV];   // joint range and velocity limit, built once per launch from the staged model
     float inv_h;                   // 1 / h with its Newton step, as quad_step takes it every substep
     int r;                         // lane & 3: the joint of a vector this lane holds
+    // ... and the scalars of the substep that are the same for the whole launch.  Read where they are used (through launder) each
+    // cost the lone owner wavefront an LDS round trip per substep with nothing else in flight, and the flags - arriving in vector
+    // registers through a laundered address - made exec-masked regions of the drive-mode choice, the gravity term and the loop bound
+    float h, kd, kdh;              // substep length, drive damping, kd * h (quad_step's product)
+    int substeps;                  // wave-uniform
+    bool velocity_drive;           // wave-uniform: tau = kd (target - qd); else the effort drive, tau = target - kd qd
+    OF a0;                         // oct_base_accel: the outward pass starts here
     template <class M>
     __device__ __forceinline__ OctAbaJv(const OctAba &ab, M &m) : OctAba(ab) {
         r = (int)(threadIdx.x & 3u);
-        inv_h = frcp(m.h);
+        h = m.h;
+        kd = m.kd;
+        kdh = kd * h;
+        inv_h = frcp(h);
+        substeps = uniform(m.substeps);
+        velocity_drive = uniform(m.drive_mode) == kDriveVelocity;
+        a0 = 0.f;
+        if (uniform(m.gravity_on)) a0 = ol.lin * qsel(-m.g[0], -m.g[1], -m.g[2]);
 #pragma unroll
         for (int v = 0; v < NV; v++) {
             const int j = 4 * v + r;
@@ -637,15 +662,14 @@ struct OctAbaJv : OctAba {
     // One simulator step, quad_step's (mppi_quad.hpp) for an all-revolute tree in velocity or effort mode: Q, QD, TGT joint vectors.
     // The substep restates quad_step's - the drive, the limit test, the second solve (octet layout: no shift of the origin) - on
     // joint vectors; the integration is the shared quad_integrate.  A change to quad_step's substep belongs here too.
+    // Of the model it reads the body blocks only: the drive, the step length, the loop bound and gravity are the members above.
     template <class TT, class M>
     __device__ __forceinline__ void step(M &m0, QPose<TT, 0> &P, OF *Q, OF *QD, const OF *TGT) const {
         M *mp = &m0;
-        for (int s = 0; s < m0.substeps; s++) {
-            M &m = *launder(mp);
-            const float h = m.h, kd = m.kd;
-            OF TAU[NV], QDD[NV], tau[NB], kdh[NB], qdd[NB], tt[NB];
+        for (int s = 0; s < substeps; s++) {
+            OF TAU[NV], QDD[NV], tau[NB], kdhs[NB], qdd[NB], tt[NB];
             JointLimits lim[NB];
-            if (m.drive_mode == kDriveVelocity) {
+            if (velocity_drive) {
 #pragma unroll
                 for (int v = 0; v < NV; v++) TAU[v] = kd * (TGT[v] - QD[v]);
             } else {
@@ -653,19 +677,18 @@ struct OctAbaJv : OctAba {
                 for (int v = 0; v < NV; v++) TAU[v] = TGT[v] - kd * QD[v];
             }
             static_for<0, NB>([&](auto ic) MPPI_LAMBDA { tau[ic] = joint<ic>(TAU); });
-            const OF kdhq = kd * h;
-            static_for<0, NB>([&](auto ic) MPPI_LAMBDA { kdh[ic] = kdhq; });
+            static_for<0, NB>([&](auto ic) MPPI_LAMBDA { kdhs[ic] = kdh; });
             OF excess = -INFINITY;
-            oct_aba<T, true, true>(m, bodies, ol, P, QD, tau, kdh, qdd, lim, tt, &excess);
+            oct_aba<T, true, true>(bodies, ol, P, QD, tau, kdhs, qdd, lim, a0, tt, &excess);
             if (qany_gt(excess, 0.f)) {   // a drive beyond its effort limit (rare): held at the bound, solved again - quad_step
                 static_for<0, NB>([&](auto ic) MPPI_LAMBDA {
                     constexpr int i = ic;
                     const OF eff = lim[i].effort;
                     const bool sat = qany_gt(qabs(tt[i]), eff);
                     tau[i] = sat ? qwhere_gt(tt[i], 0.f, eff, -eff) : tau[i];
-                    kdh[i] = sat ? 0.f : kdh[i];
+                    kdhs[i] = sat ? 0.f : kdhs[i];
                 });
-                oct_aba<T, false, true>(*launder(mp), bodies, ol, P, QD, tau, kdh, qdd, lim);
+                oct_aba<T, false, true>(bodies, ol, P, QD, tau, kdhs, qdd, lim, a0);
             }
             // the kinematic blocks of the NEXT pose: their round trip runs under the integration's arithmetic
             BodyK0 blk0[NB];

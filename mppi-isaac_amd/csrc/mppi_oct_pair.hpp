@@ -44,6 +44,8 @@ __device__ __forceinline__ void pair_owner(M &m0, CCfg &cfg0, CCost &cost0, cons
     const int H = cfg0.H, kind = cost0.kind, link = cost0.link[0], viz_link = cfg0.viz_link;
     const bool cmd_identity = m0.cmd_identity != 0, need_link = kind == kCostPandaReach, point = kind == kCostPointReach;
     const bool own_viz = want_viz && (viz_link != link || !need_link);
+    // the bodies that carry the cost link and the visualised link: resolved here, the steps keep the uniform select of the pose
+    const int link_body = need_link ? quad_link_body<T>(m0, link) : -1, viz_body = own_viz ? quad_link_body<T>(m0, viz_link) : -1;
     constexpr bool JV = AB::kJointVectors;     // (mppi_oct.hpp OctAbaJv: joint 4v + r in lane r of register v)
     constexpr int NS = JV ? (NB + 3) / 4 : NB;
     static_assert(!JV || (NS * 4 <= kStride && NB == MAXC), "joint vectors: the table row holds a word per lane of every vector");
@@ -102,7 +104,7 @@ __device__ __forceinline__ void pair_owner(M &m0, CCfg &cfg0, CCost &cost0, cons
         if (need_link) {
             QM3 Rb;
             QF pb;
-            quad_link_body_pose<T>(*launder(mp), P, link, Rb, pb);
+            quad_link_body_pose_at<T>(P, link_body, Rb, pb);
             xa[s] = f32x4{Rb.c[0], Rb.c[1], Rb.c[2], pb};
         } else if (point) {
             if constexpr (JV) xa[s] = f32x4{ab.template joint<0>(q), ab.template joint<(NB > 1 ? 1 : 0)>(q), 0.f, 0.f};
@@ -111,7 +113,7 @@ __device__ __forceinline__ void pair_owner(M &m0, CCfg &cfg0, CCost &cost0, cons
         if (own_viz) {
             QM3 Rb;
             QF pb;
-            quad_link_body_pose<T>(*launder(mp), P, viz_link, Rb, pb);
+            quad_link_body_pose_at<T>(P, viz_body, Rb, pb);
             xb[s] = f32x4{Rb.c[0], Rb.c[1], Rb.c[2], pb};
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the hand-over is in LDS before this wavefront arrives

@@ -850,15 +850,26 @@ MPPI_HD void quad_link_from_body(LK &L, const QM3 &Rb, QF pb, QM3 &R, QF &p) {
     for (int c = 0; c < 3; c++) R.c[c] = Rb.c[0] * L.R[c] + Rb.c[1] * L.R[3 + c] + Rb.c[2] * L.R[6 + c];
     p = pb + Rb.c[0] * L.p[0] + Rb.c[1] * L.p[1] + Rb.c[2] * L.p[2];
 }
-// world pose of the body that carries link l (wave-uniform choice)
-template <class T, class M, int JT>
-MPPI_HD void quad_link_body_pose(M &m, const QPose<T, JT> &P, int l, QM3 &Rb, QF &pb) {
+// the body that carries link l, as quad_body_pose takes it (wave-uniform; -1: the base).  A constant of the launch: a rollout
+// resolves it once in front of its horizon loop
+template <class T, class M>
+MPPI_HD int quad_link_body(M &m, int l) {
 #if defined(__HIP_DEVICE_COMPILE__)
     const int body = __builtin_amdgcn_readfirstlane(m.l[l].body);  // (from the LDS copy of the model it arrives in a vector register)
 #else
     const int body = m.l[l].body;
 #endif
-    quad_body_pose<T, JT, -1, T::NB>(P, body < 0 ? -1 : (body < T::NB ? body : T::NB - 1), Rb, pb);
+    return body < 0 ? -1 : (body < T::NB ? body : T::NB - 1);
+}
+// world pose of the body that carries a link, by the index quad_link_body resolved: the uniform select alone
+template <class T, int JT>
+MPPI_HD void quad_link_body_pose_at(const QPose<T, JT> &P, int body, QM3 &Rb, QF &pb) {
+    quad_body_pose<T, JT, -1, T::NB>(P, body, Rb, pb);
+}
+// world pose of the body that carries link l (wave-uniform choice)
+template <class T, class M, int JT>
+MPPI_HD void quad_link_body_pose(M &m, const QPose<T, JT> &P, int l, QM3 &Rb, QF &pb) {
+    quad_link_body_pose_at<T>(P, quad_link_body<T>(m, l), Rb, pb);
 }
 // world pose of link l: row r of R (standard) and component r of p
 template <class T, class M, int JT>
