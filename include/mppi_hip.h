@@ -627,6 +627,32 @@ int mppi_sim_floating_link_acceleration(mppi_ctx_t *ctx, int rb_first, int rb_co
                                         float *acc_dev /* [K][rb_count][6] */);
 int mppi_sim_floating_wrench_forces(mppi_ctx_t *ctx, int rb_first, int rb_count, const float *wrench_dev /* [K][rb_count][6] */,
                                     float *tau_dev /* [K][6 + n_dof] */);
+/* THE ROBOT AS A WHOLE: where its centre of mass is, what momentum it carries, how much energy it holds - per env, at the envs'
+ * current state (the state mppi_sim_materialise reports), world axes, env-major device tensors.  "The robot" is what the packed
+ * model moves: its n_bodies bodies and, for a moving base, the base's own rigid body (base_mass / base_h / base_Io); for a
+ * fixed-base forest the whole forest.  Free box and sphere actors are no part of it.  DEVIATION: a link welded to a FIXED base
+ * does not move and is not counted - neither its mass nor its weight shows in any column.
+ * Row k of mppi_sim_momentum:  column 0 the total mass m;  1:4 the centre of mass c;  4:7 the linear momentum p = m c';  7:10
+ * the angular momentum L about c;  10 the kinetic energy T;  11 the potential energy V = -m g . c with the model's g, as the steps
+ * take it - exactly 0 for an actor with gravity: false.  The one entry serves fixed bases, fixed-base forests and ONE moving base;
+ * with a moving base every env reads its own base pose and twist (columns 0:7 and 7:13 of its root row).  The sums are taken about
+ * the base origin on the relative offsets the other routines walk, and the base position is added to c once, at the end: m, p, L,
+ * T and c - p_base do not depend on where the base stands.
+ * The centroidal momentum matrix A, A v = (p, L) of that row: rows 0-2 linear (A[0:3] / m is the Jacobian of the centre of mass),
+ * rows 3-5 angular about c.  v = qd for a fixed base (mppi_sim_centroidal_matrix); v = (root linvel, root angvel, qd) of
+ * mppi_sim_floating_jacobian for a moving one (mppi_sim_floating_centroidal_matrix).  Column i is the spatial momentum of the
+ * composite body below joint i under a unit joint rate, moved to c.  For a moving base, with r = c - p_base and the M of
+ * mppi_sim_floating_mass_matrix:  A[0:3] = M[0:3, :],  A[3:6] = M[3:6, :] - [r]x M[0:3, :]  (the block under the base's linear
+ * velocity is zero and is written as exact zeros).
+ * Each entry is ONE launch on the context's stream - no allocation, no copy, no synchronise: it can sit in a captured graph.
+ * MPPI_EINVAL: a null output.  MPPI_EUNSUPPORTED (mppi_last_error says which): a forest of several moving bases (n_extra_bases >
+ * 0), a kinematic tree whose launch table lacks the kernel; for the two matrix entries the wrong kind of base - the text names the
+ * other entry.  Refused before any launch.  NOT here: the rate of the centroidal momentum (A' v), the reaction wrench of a fixed
+ * mount. */
+#define MPPI_MOMENTUM_FLOATS 12
+int mppi_sim_momentum(mppi_ctx_t *ctx, float *out_dev /* [K][12] */);
+int mppi_sim_centroidal_matrix(mppi_ctx_t *ctx, float *A_dev /* [K][6][n_dof] */);
+int mppi_sim_floating_centroidal_matrix(mppi_ctx_t *ctx, float *A_dev /* [K][6][6 + n_dof] */);
 int mppi_sim_accumulate_cost(mppi_ctx_t *ctx, int t, const float *cost_dev); /* S += gamma^t c      */
 int mppi_sim_finish(mppi_ctx_t *ctx);                      /* S += control cost                     */
 /* The same horizon in TWO launches for host-side costs that are functions of the state tensors (mppi_isaac.py:57-69 evaluates

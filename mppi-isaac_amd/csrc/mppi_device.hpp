@@ -1949,4 +1949,217 @@ MPPI_HD void floating_wrench_joint_forces(const Pose<T> &P, const V3 *d, V3 *F, 
     wrench_joint_forces_pass<true, T>(P, d, F, N, Fb, Nb, tau);
 }
 
+// ---- the robot as a whole, one env: centre of mass, momentum and energy (mppi_sim_momentum) and the centroidal momentum matrix
+// ---- (mppi_sim_centroidal_matrix / mppi_sim_floating_centroidal_matrix), of a FIXED-base robot and of a robot with ONE moving base ----
+enum { kMomentumFloats = 12 };  // MPPI_MOMENTUM_FLOATS (include/mppi_hip.h)
+
+// out [12] = (m, c [3], p [3], L about c [3], T, V) of the bodies the packed model moves, world axes, at the joint rates qd [NB].
+// Outward, every body takes its angular velocity and the velocity of ITS OWN origin from its parent through d[i] (a prismatic
+// joint adds qd a_i to the latter).  Inward, each body's own m, first moment h = m (com - p_i), linear momentum m v + w x h and
+// angular momentum about p_i, I w + h x v, join what its subtrees handed it and move to the parent's origin by the same relative
+// offset: h' = h + m d, L' = L + d x p.  The sums arrive about the BASE ORIGIN; only there r = h / m = c - p_base is formed, L
+// moved to c (L - r x p) and p_base added to c, once: m, p, L, T and c - p_base do not depend on where the base stands.
+// T = sum (v . p_i + w . L_i) / 2 over the bodies' own momenta; V = -m g . c with the model's g, exactly 0 without gravity.
+//
+// MOVING = true (floating_momentum): v [6 + NB] = (root linvel, root angvel, qd) of floating_link_jacobian; the bodies next to the
+// base ride on its twist, and the base's own rigid body (base_m, base_hb, base_Ic) is the first term of every sum.  With a fixed
+// base the sums start from zero: what is welded to a base that does not move is not part of the robot.
+template <bool MOVING, class T, class M>
+MPPI_HD void momentum_pass(M &m0, const Pose<T> &P, const V3 *d, const float *v, float *out) {
+    constexpr int NB = T::NB, C0 = MOVING ? 6 : 0;
+    constexpr int NA = NB ? NB : 1;
+    M *mp = &m0;
+    const V3 zero = {0.f, 0.f, 0.f};
+    V3 vb = zero, wb = zero;  // MOVING: the velocity of the base origin and the base's angular velocity
+    float mt = 0.f, T2 = 0.f;  // the whole robot about the base origin: mass, twice the kinetic energy,
+    V3 ht = zero, pt = zero, Lt = zero;  // first moment, linear momentum, angular momentum
+    if constexpr (MOVING) {  // the base's own rigid body
+        vb = V3{v[0], v[1], v[2]};
+        wb = V3{v[3], v[4], v[5]};
+        const float hb3[3] = {m0.base_hb[0], m0.base_hb[1], m0.base_hb[2]};
+        const float Ic6[6] = {m0.base_Ic[0], m0.base_Ic[1], m0.base_Ic[2], m0.base_Ic[3], m0.base_Ic[4], m0.base_Ic[5]};
+        S3 Io;
+        mt = m0.base_m;
+        rigid_inertia_about_origin(P.Rb, hb3, Ic6, mt > 0.f ? 1.f / mt : 0.f, ht, Io);
+        pt = mt * vb + cross(wb, ht);
+        Lt = mul(Io, wb) + cross(ht, vb);
+        T2 = dot(vb, pt) + dot(wb, Lt);
+    }
+    V3 w[NA], vo[NA];  // angular velocity, velocity of the body origin
+    static_for<0, NB>([&](auto ic) MPPI_LAMBDA {
+        constexpr int i = ic;
+        constexpr int par = T::par[i];
+        constexpr int pj = par < 0 ? 0 : par;
+        const V3 az = {P.R[i].a[2], P.R[i].a[5], P.R[i].a[8]};
+        const bool rev = P.jt[i] == 0;
+        const V3 wp = par < 0 ? wb : w[pj], vp = par < 0 ? vb : vo[pj];
+        const V3 sv = v[C0 + i] * az;
+        const V3 ride = vp + cross(wp, d[i]);  // the origin rides on the parent at d[i]
+        w[i] = rev ? wp + sv : wp;
+        vo[i] = rev ? ride : ride + sv;
+    });
+    float cm[NA];
+    V3 ch[NA], cp[NA], cL[NA];
+    static_rfor<0, NB>([&](auto ic) MPPI_LAMBDA {
+        constexpr int i = ic;
+        constexpr int par = T::par[i];
+        constexpr int pj = par < 0 ? 0 : par;
+        const BodyK1 b = load_block<BodyK1>(launder(mp)->b[i].k1);  // (fetched where it is used, as in mass_matrix)
+        const float hb3[3] = {b.hb(0), b.hb(1), b.hb(2)}, Ic6[6] = {b.Ic(0), b.Ic(1), b.Ic(2), b.Ic(3), b.Ic(4), b.Ic(5)};
+        V3 h;
+        S3 I;
+        rigid_inertia_about_origin(P.R[i], hb3, Ic6, b.invm, h, I);
+        // the body's own momenta: linear, and angular about p_i
+        const V3 pl = b.m * vo[i] + cross(w[i], h);
+        const V3 la = mul(I, w[i]) + cross(h, vo[i]);
+        T2 += dot(vo[i], pl) + dot(w[i], la);
+        float mc = b.m;
+        V3 hc = h, pc = pl, Lc = la;
+        if constexpr (last_child<T>(i) >= 0) {  // the subtrees below, already about p_i
+            mc += cm[i];
+            hc = hc + ch[i];
+            pc = pc + cp[i];
+            Lc = Lc + cL[i];
+        }
+        // to the parent's origin (a body next to the base: to the base origin)
+        const V3 hp = hc + mc * d[i], Lp = Lc + cross(d[i], pc);
+        if constexpr (par < 0) {
+            mt += mc;
+            ht = ht + hp;
+            pt = pt + pc;
+            Lt = Lt + Lp;
+        } else if constexpr (last_child<T>(pj) == i) {
+            cm[pj] = mc;
+            ch[pj] = hp;
+            cp[pj] = pc;
+            cL[pj] = Lp;
+        } else {
+            cm[pj] += mc;
+            ch[pj] = ch[pj] + hp;
+            cp[pj] = cp[pj] + pc;
+            cL[pj] = cL[pj] + Lp;
+        }
+    });
+    const V3 r = (mt > 0.f ? 1.f / mt : 0.f) * ht;  // c - p_base
+    const V3 c = P.pb + r, L = Lt - cross(r, pt);
+    out[0] = mt;
+    out[1] = c.x; out[2] = c.y; out[3] = c.z;
+    out[4] = pt.x; out[5] = pt.y; out[6] = pt.z;
+    out[7] = L.x; out[8] = L.y; out[9] = L.z;
+    out[10] = 0.5f * T2;
+    out[11] = m0.gravity_on != 0 ? -(mt * dot(V3{m0.g[0], m0.g[1], m0.g[2]}, c)) : 0.f;
+}
+// qd [NB]
+template <class T, class M>
+MPPI_HD void momentum(M &m0, const Pose<T> &P, const V3 *d, const float *qd, float *out) { momentum_pass<false, T>(m0, P, d, qd, out); }
+// v [6 + NB] = (root linvel, root angvel, qd)
+template <class T, class M>
+MPPI_HD void floating_momentum(M &m0, const Pose<T> &P, const V3 *d, const float *v, float *out) { momentum_pass<true, T>(m0, P, d, v, out); }
+
+// A [6][NB] (row-major): the centroidal momentum matrix, A qd = (p, L about c) of momentum.  Column i is the spatial momentum of the
+// composite body below joint i under a unit joint rate - the composite inertias (mass, first moment, rotational inertia about the
+// body's own origin) are the very sums of mass_matrix, handed inward by the same rule -: f = a x h (revolute) or m a (prismatic),
+// and the angular momentum about p_i, I a or h x a.  The composites go on to the base origin, where r = h / m = c - p_base of the
+// whole robot is known; a second walk, outward, sums the offsets to p_i - p_base and moves every column's moment by
+// (p_i - p_base) - r to the centre of mass.  Relative offsets only: A does not depend on where the base stands.
+//
+// MOVING = true (floating_centroidal_matrix): A [6][6 + NB] in v = (root linvel, root angvel, qd); the base's own rigid body joins
+// the sums, and the six base columns are the momentum of the WHOLE robot moving as one body: rows 0-2 [m 1, -[h]x], rows 3-5
+// [0, I_c] with I_c = I_o - ((h . r) 1 - h r^T) - the shifted rows M[3:6] - [r]x M[0:3] of floating_mass_matrix, whose block
+// [h]x - m [r]x is zero (a translation of the whole robot carries no angular momentum about c) and is written as zeros.
+template <bool MOVING, class T, class M>
+MPPI_HD void centroidal_matrix_pass(M &m0, const Pose<T> &P, const V3 *d, float *A) {
+    constexpr int NB = T::NB, C0 = MOVING ? 6 : 0, LD = C0 + NB;
+    constexpr int NA = NB ? NB : 1;
+    M *mp = &m0;
+    float cm[NA];
+    V3 ch[NA];
+    S3 cI[NA];
+    float bm = 0.f;  // the whole robot about the base origin
+    V3 bh = {0.f, 0.f, 0.f};
+    S3 bI = {};
+    if constexpr (MOVING) {
+        bm = m0.base_m;
+        const float hb3[3] = {m0.base_hb[0], m0.base_hb[1], m0.base_hb[2]};
+        const float Ic6[6] = {m0.base_Ic[0], m0.base_Ic[1], m0.base_Ic[2], m0.base_Ic[3], m0.base_Ic[4], m0.base_Ic[5]};
+        rigid_inertia_about_origin(P.Rb, hb3, Ic6, bm > 0.f ? 1.f / bm : 0.f, bh, bI);
+    }
+    static_rfor<0, NB>([&](auto ic) MPPI_LAMBDA {
+        constexpr int i = ic;
+        constexpr int par = T::par[i];
+        constexpr int pj = par < 0 ? 0 : par;
+        const BodyK1 b = load_block<BodyK1>(launder(mp)->b[i].k1);  // (fetched where it is used, as in mass_matrix)
+        const M3 &R = P.R[i];
+        const float hb3[3] = {b.hb(0), b.hb(1), b.hb(2)}, Ic6[6] = {b.Ic(0), b.Ic(1), b.Ic(2), b.Ic(3), b.Ic(4), b.Ic(5)};
+        V3 h;
+        S3 I;
+        rigid_inertia_about_origin(R, hb3, Ic6, b.invm, h, I);
+        float mc = b.m;
+        V3 hc = h;
+        if constexpr (last_child<T>(i) >= 0) {  // the subtrees below, already about p_i
+            mc += cm[i];
+            hc = hc + ch[i];
+            I.xx += cI[i].xx; I.xy += cI[i].xy; I.xz += cI[i].xz; I.yy += cI[i].yy; I.yz += cI[i].yz; I.zz += cI[i].zz;
+        }
+        // spatial momentum (linear f, angular n about p_i) of the composite body under a unit rate of joint i
+        const V3 az = {R.a[2], R.a[5], R.a[8]};
+        const bool rev = P.jt[i] == 0;
+        const V3 f = rev ? cross(az, hc) : mc * az;
+        const V3 n = rev ? mul(I, az) : cross(hc, az);
+        A[0 * LD + C0 + i] = f.x; A[1 * LD + C0 + i] = f.y; A[2 * LD + C0 + i] = f.z;
+        A[3 * LD + C0 + i] = n.x; A[4 * LD + C0 + i] = n.y; A[5 * LD + C0 + i] = n.z;
+        // to the parent's origin: h' = h + m d, I' = I + 2 (e.d) 1 - (e d^T + d e^T) with e = h + m d / 2
+        const V3 dd = d[i];
+        const V3 e = hc + (0.5f * mc) * dd;
+        const float ed = 2.f * dot(e, dd);
+        S3 Ip;
+        Ip.xx = I.xx + ed - 2.f * e.x * dd.x;
+        Ip.yy = I.yy + ed - 2.f * e.y * dd.y;
+        Ip.zz = I.zz + ed - 2.f * e.z * dd.z;
+        Ip.xy = I.xy - (e.x * dd.y + dd.x * e.y);
+        Ip.xz = I.xz - (e.x * dd.z + dd.x * e.z);
+        Ip.yz = I.yz - (e.y * dd.z + dd.y * e.z);
+        const V3 hp = hc + mc * dd;
+        if constexpr (par < 0) {  // next to the base: to the base origin
+            bm += mc;
+            bh = bh + hp;
+            bI.xx += Ip.xx; bI.xy += Ip.xy; bI.xz += Ip.xz; bI.yy += Ip.yy; bI.yz += Ip.yz; bI.zz += Ip.zz;
+        } else if constexpr (last_child<T>(pj) == i) {
+            cm[pj] = mc;
+            ch[pj] = hp;
+            cI[pj] = Ip;
+        } else {
+            cm[pj] += mc;
+            ch[pj] = ch[pj] + hp;
+            cI[pj].xx += Ip.xx; cI[pj].xy += Ip.xy; cI[pj].xz += Ip.xz; cI[pj].yy += Ip.yy; cI[pj].yz += Ip.yz; cI[pj].zz += Ip.zz;
+        }
+    });
+    const V3 r = (bm > 0.f ? 1.f / bm : 0.f) * bh;  // c - p_base
+    V3 ro[NA];  // p_i - p_base
+    static_for<0, NB>([&](auto ic) MPPI_LAMBDA {
+        constexpr int i = ic;
+        constexpr int par = T::par[i];
+        constexpr int pj = par < 0 ? 0 : par;
+        ro[i] = par < 0 ? d[i] : ro[pj] + d[i];
+        const V3 f = {A[0 * LD + C0 + i], A[1 * LD + C0 + i], A[2 * LD + C0 + i]};
+        const V3 n = V3{A[3 * LD + C0 + i], A[4 * LD + C0 + i], A[5 * LD + C0 + i]} + cross(ro[i] - r, f);  // the same momentum about c
+        A[3 * LD + C0 + i] = n.x; A[4 * LD + C0 + i] = n.y; A[5 * LD + C0 + i] = n.z;
+    });
+    if constexpr (MOVING) {
+        const float hr = dot(bh, r);
+        const float B[6][6] = {{bm, 0.f, 0.f, 0.f, bh.z, -bh.y},
+                               {0.f, bm, 0.f, -bh.z, 0.f, bh.x},
+                               {0.f, 0.f, bm, bh.y, -bh.x, 0.f},
+                               {0.f, 0.f, 0.f, bI.xx - (hr - bh.x * r.x), bI.xy + bh.x * r.y, bI.xz + bh.x * r.z},
+                               {0.f, 0.f, 0.f, bI.xy + bh.x * r.y, bI.yy - (hr - bh.y * r.y), bI.yz + bh.y * r.z},
+                               {0.f, 0.f, 0.f, bI.xz + bh.x * r.z, bI.yz + bh.y * r.z, bI.zz - (hr - bh.z * r.z)}};
+        for (int a = 0; a < 6; a++)
+            for (int c = 0; c < 6; c++) A[a * LD + c] = B[a][c];
+    }
+}
+template <class T, class M>
+MPPI_HD void centroidal_matrix(M &m0, const Pose<T> &P, const V3 *d, float *A) { centroidal_matrix_pass<false, T>(m0, P, d, A); }
+template <class T, class M>
+MPPI_HD void floating_centroidal_matrix(M &m0, const Pose<T> &P, const V3 *d, float *A) { centroidal_matrix_pass<true, T>(m0, P, d, A); }
+
 }  // namespace mppi

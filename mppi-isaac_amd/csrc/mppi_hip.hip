@@ -1526,6 +1526,58 @@ int mppi_sim_floating_wrench_forces(mppi_ctx_t *c, int rb_first, int rb_count, c
     e->sim_floating_wrench_forces(c, rb_first, rb_count, wrench_dev, tau_dev);
     return launch_check();
 }
+namespace {
+// the launch-table row for the entries about the robot as a whole: a fixed base (fixed-base forests too) or ONE moving base; a
+// forest of several moving bases is refused before any launch
+int whole_robot_entry(mppi_ctx *c, const char *what, const TopoEntry *&e) {
+    if (c->hm.n_bases > 1)
+        return fail(MPPI_EUNSUPPORTED, std::string(what) + ": unsupported for a forest of several moving bases (" + std::to_string(c->hm.n_bases) +
+                                       " bases: the momentum of each robot is not computed); one moving-base robot per env only");
+    int parents[MPPI_MAX_BODIES];
+    for (int i = 0; i < c->hm.nb; i++) parents[i] = c->hm.b[i].k0.parent;
+    e = find_entry(c->hm.nb, parents, c->scene, c->hm.n_free);
+    if (!e) return fail(MPPI_EUNSUPPORTED, std::string(what) + ": not available for this kinematic tree");
+    return MPPI_OK;
+}
+}  // namespace
+static_assert(kMomentumFloats == MPPI_MOMENTUM_FLOATS, "floats per row of mppi_sim_momentum");
+/* mass, centre of mass, momentum and energy of the robot of every env: one launch on the context's stream, no allocation, no copy,
+ * no synchronise (include/mppi_hip.h) */
+int mppi_sim_momentum(mppi_ctx_t *c, float *out_dev) {
+    CTX_TRY(c);
+    if (!out_dev) return fail(MPPI_EINVAL, "mppi_sim_momentum: null output");
+    const TopoEntry *e = nullptr;
+    if (int rc = whole_robot_entry(c, "mppi_sim_momentum", e)) return rc;
+    const auto launch = c->hm.floating ? e->sim_floating_momentum : e->sim_momentum;
+    if (!launch) return fail(MPPI_EUNSUPPORTED, "mppi_sim_momentum: not available for this kinematic tree");
+    launch(c, out_dev);
+    return launch_check();
+}
+/* the centroidal momentum matrix, A v = (p, L) of mppi_sim_momentum: one launch each */
+int mppi_sim_centroidal_matrix(mppi_ctx_t *c, float *A_dev) {
+    CTX_TRY(c);
+    if (!A_dev) return fail(MPPI_EINVAL, "mppi_sim_centroidal_matrix: null output");
+    const TopoEntry *e = nullptr;
+    if (int rc = whole_robot_entry(c, "mppi_sim_centroidal_matrix", e)) return rc;
+    if (c->hm.floating)
+        return fail(MPPI_EUNSUPPORTED, "mppi_sim_centroidal_matrix: this robot has a moving base (the six base columns are not computed); use "
+                                       "mppi_sim_floating_centroidal_matrix for a robot with one moving base");
+    if (!e->sim_centroidal_matrix) return fail(MPPI_EUNSUPPORTED, "mppi_sim_centroidal_matrix: not available for this kinematic tree");
+    e->sim_centroidal_matrix(c, A_dev);
+    return launch_check();
+}
+int mppi_sim_floating_centroidal_matrix(mppi_ctx_t *c, float *A_dev) {
+    CTX_TRY(c);
+    if (!A_dev) return fail(MPPI_EINVAL, "mppi_sim_floating_centroidal_matrix: null output");
+    const TopoEntry *e = nullptr;
+    if (int rc = whole_robot_entry(c, "mppi_sim_floating_centroidal_matrix", e)) return rc;
+    if (!c->hm.floating)
+        return fail(MPPI_EUNSUPPORTED, "mppi_sim_floating_centroidal_matrix: this robot has a fixed base (there are no base columns); use "
+                                       "mppi_sim_centroidal_matrix for fixed-base robots and fixed-base forests");
+    if (!e->sim_floating_centroidal_matrix) return fail(MPPI_EUNSUPPORTED, "mppi_sim_floating_centroidal_matrix: not available for this kinematic tree");
+    e->sim_floating_centroidal_matrix(c, A_dev);
+    return launch_check();
+}
 int mppi_sim_accumulate_cost(mppi_ctx_t *c, int t, const float *cost_dev) {
     CTX_TRY(c);
     if (!cost_dev) return fail(MPPI_EINVAL, "null cost");

@@ -2199,6 +2199,79 @@ __global__ __launch_bounds__(kWave) void k_sim_floating_wrench_forces(const DevM
     __syncthreads();
     store_staged_rows<kLen>(s_row, n_rows, out + (size_t)k0 * kLen, kLen);
 }
+// ---- the robot as a whole (mppi_sim_momentum / mppi_sim_centroidal_matrix / mppi_sim_floating_centroidal_matrix) ----
+// out [K][12] = (m, c, p, L about c, T, V) of every env (momentum / floating_momentum, mppi_device.hpp).  MOVING: the contact-scene
+// unit's instantiation for a robot with one moving base - every env reads ITS OWN base rows, the pose as sim_env_pose does, the
+// twist - columns 7:13 - here; with a fixed base (the contact-free unit's instantiation) no velocity of any actor's root row is
+// read.  Rows go out through the LDS tile; rows past K - 1 of the last wavefront are neither computed nor stored.
+template <class T, bool MOVING = false>
+__global__ __launch_bounds__(kWave) void k_sim_momentum(const DevModel *__restrict__ m, int K, const float *__restrict__ x0_root,
+                                                        const float *__restrict__ q_, const float *__restrict__ qd_, const float *__restrict__ base_,
+                                                        float *__restrict__ out) {
+    constexpr int NB = T::NB, C0 = MOVING ? 6 : 0, kLen = kMomentumFloats, kStride = staged_stride(kLen);
+    __shared__ float s_row[kWave * kStride];
+    CModel &M = *(CModel *)m;
+    const int k0 = blockIdx.x * kWave, k = k0 + threadIdx.x;
+    const int n_rows = K - k0 < kWave ? K - k0 : kWave;
+    if (k < K) {
+        Pose<T> P;
+        V3 d[NB ? NB : 1];
+        float v[C0 + NB ? C0 + NB : 1], row[kLen];
+        sim_env_pose<T>(M, K, k, x0_root, q_, base_, P, d);
+        if constexpr (MOVING)
+            for (int j = 0; j < 6; j++) v[j] = base_[(size_t)(7 + j) * K + k];
+        static_for<0, NB>([&](auto ic) {
+            constexpr int i = ic;
+            v[C0 + i] = qd_[(size_t)i * K + k];
+        });
+        if constexpr (MOVING) floating_momentum<T>(M, P, d, v, row);
+        else momentum<T>(M, P, d, v, row);
+        static_for<0, kLen>([&](auto jc) {
+            constexpr int j = jc;
+            s_row[threadIdx.x * kStride + j] = row[j];
+        });
+    }
+    __syncthreads();
+    store_staged_rows<kLen>(s_row, n_rows, out + (size_t)k0 * kLen, kLen);
+}
+// out [K][6][n]: the centroidal momentum matrix of every env of a fixed-base robot (centroidal_matrix, mppi_device.hpp), built in
+// the lane's row of the tile as k_sim_mass_matrix builds M
+template <class T>
+__global__ __launch_bounds__(kWave) void k_sim_centroidal_matrix(const DevModel *__restrict__ m, int K, const float *__restrict__ x0_root,
+                                                                 const float *__restrict__ q_, const float *__restrict__ base_, float *__restrict__ out) {
+    constexpr int kLen = 6 * T::NB, kStride = staged_stride(kLen);
+    __shared__ float s_row[kWave * kStride];
+    CModel &M = *(CModel *)m;
+    const int k0 = blockIdx.x * kWave, k = k0 + threadIdx.x;
+    const int n_rows = K - k0 < kWave ? K - k0 : kWave;
+    if (k < K) {
+        Pose<T> P;
+        V3 d[T::NB ? T::NB : 1];
+        sim_env_pose<T>(M, K, k, x0_root, q_, base_, P, d);
+        centroidal_matrix<T>(M, P, d, s_row + threadIdx.x * kStride);
+    }
+    __syncthreads();
+    store_staged_rows<kLen>(s_row, n_rows, out + (size_t)k0 * kLen, kLen);
+}
+// out [K][6][6 + n]: the same matrix in v = (root linvel, root angvel, qd) for a robot with one moving base (floating_centroidal_matrix)
+template <class T>
+__global__ __launch_bounds__(kWave) void k_sim_floating_centroidal_matrix(const DevModel *__restrict__ m, int K, const float *__restrict__ x0_root,
+                                                                          const float *__restrict__ q_, const float *__restrict__ base_,
+                                                                          float *__restrict__ out) {
+    constexpr int kLen = 6 * (6 + T::NB), kStride = staged_stride(kLen);
+    __shared__ float s_row[kWave * kStride];
+    CModel &M = *(CModel *)m;
+    const int k0 = blockIdx.x * kWave, k = k0 + threadIdx.x;
+    const int n_rows = K - k0 < kWave ? K - k0 : kWave;
+    if (k < K) {
+        Pose<T> P;
+        V3 d[T::NB ? T::NB : 1];
+        sim_env_pose<T>(M, K, k, x0_root, q_, base_, P, d);
+        floating_centroidal_matrix<T>(M, P, d, s_row + threadIdx.x * kStride);
+    }
+    __syncthreads();
+    store_staged_rows<kLen>(s_row, n_rows, out + (size_t)k0 * kLen, kLen);
+}
 
 // Parity / debug entry (mppi_eval_cost): the cost program of the context evaluated by the interpreter the rollout kernels run
 // (program_cost_with, mppi_device.hpp) on CALLER-GIVEN simulator answers - reference-layout rows of n envs - instead of the
@@ -2406,6 +2479,13 @@ struct TopoEntry {
     void (*sim_floating_link_acceleration)(mppi_ctx *, int, int, const float *, int, float *);
     // mppi_sim_floating_wrench_forces
     void (*sim_floating_wrench_forces)(mppi_ctx *, int, int, const float *, float *);
+    // the robot as a whole: mppi_sim_momentum serves a fixed base (sim_momentum, filled by the contact-free unit) and ONE moving base
+    // (sim_floating_momentum, filled by the contact-scene unit); the centroidal momentum matrix has an entry for each kind of base:
+    // mppi_sim_centroidal_matrix, mppi_sim_floating_centroidal_matrix
+    void (*sim_momentum)(mppi_ctx *, float *);
+    void (*sim_centroidal_matrix)(mppi_ctx *, float *);
+    void (*sim_floating_momentum)(mppi_ctx *, float *);
+    void (*sim_floating_centroidal_matrix)(mppi_ctx *, float *);
 };
 }  // namespace mppi
 
@@ -2539,6 +2619,14 @@ void launch_sim_floating_wrench_forces_t(mppi_ctx *c, int rb_first, int rb_count
                        rb_first, rb_count, w, out);
 }
 template <class T>
+void launch_sim_floating_momentum_t(mppi_ctx *c, float *out) {
+    hipLaunchKernelGGL((k_sim_momentum<T, true>), dim3(c->n_waves), dim3(kWave), 0, c->stream, c->d_model, c->K, c->d_x0_root, c->d_q, c->d_qd, c->d_base, out);
+}
+template <class T>
+void launch_sim_floating_centroidal_matrix_t(mppi_ctx *c, float *out) {
+    hipLaunchKernelGGL(k_sim_floating_centroidal_matrix<T>, dim3(c->n_waves), dim3(kWave), 0, c->stream, c->d_model, c->K, c->d_x0_root, c->d_q, c->d_base, out);
+}
+template <class T>
 hipError_t raise_lds_limit(size_t lane_bytes, size_t quad_bytes) {  // lane_bytes == 0: the one-lane kernels are not used
     auto raise = [](auto kernel, size_t bytes) { return hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); };
     hipError_t e = hipSuccess;
@@ -2636,6 +2724,16 @@ void launch_sim_wrench_forces_t(mppi_ctx *c, int rb_first, int rb_count, const f
                        c->scene ? c->d_base : nullptr, rb_first, rb_count, w, out);
 }
 template <class T>
+void launch_sim_momentum_t(mppi_ctx *c, float *out) {
+    hipLaunchKernelGGL(k_sim_momentum<T>, dim3(c->n_waves), dim3(kWave), 0, c->stream, c->d_model, c->K, c->d_x0_root, c->d_q, c->d_qd,
+                       c->scene ? c->d_base : nullptr, out);
+}
+template <class T>
+void launch_sim_centroidal_matrix_t(mppi_ctx *c, float *out) {
+    hipLaunchKernelGGL(k_sim_centroidal_matrix<T>, dim3(c->n_waves), dim3(kWave), 0, c->stream, c->d_model, c->K, c->d_x0_root, c->d_q,
+                       c->scene ? c->d_base : nullptr, out);
+}
+template <class T>
 void launch_rollout_t(mppi_ctx *c) { launch_rollout_kernel(k_rollout<T>, c->n_waves, kWave, 0, c); }
 template <class T>
 void launch_sim_step_t(mppi_ctx *c, int mode, int t, const float *u_ext) {
@@ -2681,6 +2779,8 @@ void fill_topo_entry_free(TopoEntry &e) {
         e.sim_forward_dynamics = &launch_sim_forward_dynamics_t<T>;
         e.sim_link_acceleration = &launch_sim_link_acceleration_t<T>;
         e.sim_wrench_forces = &launch_sim_wrench_forces_t<T>;
+        e.sim_momentum = &launch_sim_momentum_t<T>;
+        e.sim_centroidal_matrix = &launch_sim_centroidal_matrix_t<T>;
     }
 }
 template <class T>
@@ -2705,6 +2805,8 @@ void fill_topo_entry_scene(TopoEntry &e) {
         e.sim_floating_forward_dynamics = &launch_sim_floating_forward_dynamics_t<T>;
         e.sim_floating_link_acceleration = &launch_sim_floating_link_acceleration_t<T>;
         e.sim_floating_wrench_forces = &launch_sim_floating_wrench_forces_t<T>;
+        e.sim_floating_momentum = &launch_sim_floating_momentum_t<T>;
+        e.sim_floating_centroidal_matrix = &launch_sim_floating_centroidal_matrix_t<T>;
     }
 }
 

@@ -21,6 +21,7 @@ MPPI_OK, MPPI_EINVAL, MPPI_EHIP, MPPI_EUNSUPPORTED, MPPI_ESTATE = 0, -1, -2, -3,
 JOINT_REVOLUTE, JOINT_PRISMATIC = 0, 1
 DRIVE_VELOCITY, DRIVE_EFFORT, DRIVE_POSITION = 0, 1, 2
 ID_GRAVITY, ID_VELOCITY = 1, 2      # terms of mppi_sim_inverse_dynamics / mppi_sim_forward_dynamics (MPPI_ID_*)
+MOMENTUM_FLOATS = 12                # a row of mppi_sim_momentum: m, c [3], p [3], L about c [3], T, V (MPPI_MOMENTUM_FLOATS)
 ACTOR_ROBOT, ACTOR_BOX, ACTOR_SPHERE = 0, 1, 2
 COST_NONE, COST_POINT_REACH, COST_PANDA_REACH, COST_BOXER_PUSH, COST_PANDA_PICK, COST_PROGRAM = 0, 1, 2, 3, 4, 5
 OP_DIST, OP_TILT, OP_YAW_ABS, OP_ALIGN, OP_FORCE_L1, OP_SPEED, OP_DOF_SQ, OP_ABS_DZ, OP_BELOW = 1, 2, 3, 4, 5, 6, 7, 8, 9
@@ -166,6 +167,9 @@ _SIGNATURES = {
     "mppi_sim_floating_forward_dynamics": (C.c_int, [_vp, _vp, C.c_int, _vp]),
     "mppi_sim_floating_link_acceleration": (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_int, _vp]),
     "mppi_sim_floating_wrench_forces": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
+    "mppi_sim_momentum": (C.c_int, [_vp, _vp]),
+    "mppi_sim_centroidal_matrix": (C.c_int, [_vp, _vp]),
+    "mppi_sim_floating_centroidal_matrix": (C.c_int, [_vp, _vp]),
     "mppi_sim_accumulate_cost": (C.c_int, [_vp, C.c_int, _vp]),
     "mppi_sim_finish": (C.c_int, [_vp]),
     "mppi_rollout_trajectory": (C.c_int, [_vp]),

@@ -654,6 +654,8 @@ class IsaacGymWrapper:
         self._floating_bias_force = None                # acquire_floating_bias_force_tensor: filled by refresh_floating_bias_force_tensors()
         self._floating_free_acceleration = None         # acquire_floating_free_acceleration_tensor: filled by refresh_floating_free_acceleration_tensors()
         self._floating_link_bias_acceleration = {}      # acquire_floating_link_bias_acceleration_tensor: filled by refresh_floating_link_bias_acceleration_tensors()
+        self._momentum = None                           # acquire_momentum_tensor: filled by refresh_momentum_tensors()
+        self._centroidal_matrix = self._floating_centroidal_matrix = None   # acquire_*centroidal_matrix_tensor: filled by their refresh calls
         self._visualize_link_present = sc.viz_link_index() >= 0
         self.visualize_link_buffer = []
         if self._visualize_link_present:
@@ -1074,6 +1076,89 @@ class IsaacGymWrapper:
         out = torch.empty((self.num_envs, 6, 6 + self.scene.n_dof), dtype=torch.float32, device=self.device)
         self._physics_call(self._lib.mppi_sim_floating_jacobian, rb, 1, _dev_ptr(out), what=self._FJ_WHAT)
         return out
+
+    # ------------------------------------------------------------------ the robot as a whole: centre of mass, momentum, energy
+    # mppi_sim_momentum: one [K, 12] row per env - mass, centre of mass, linear momentum, angular momentum about the centre of mass,
+    # kinetic and potential energy, world axes - of the bodies the model moves (a moving base's own body included; free box and
+    # sphere actors and links welded to a fixed base are not).  Fixed bases, fixed-base forests and one moving base; a forest of
+    # several moving bases raises NotImplementedError with the library's text.  The centroidal momentum matrix A, A v = (p, L), has
+    # one tensor per kind of base, as J and M have; the wrong one raises NotImplementedError naming the other.
+    _MOM_WHAT = "centre of mass, momentum and energy"
+
+    def acquire_momentum_tensor(self, actor_name: str):
+        """[K, 12]: column 0 the mass, 1:4 the centre of mass, 4:7 the linear momentum, 7:10 the angular momentum about the centre
+        of mass, 10 the kinetic and 11 the potential energy (-m g . c; 0 without gravity).  Zero until refresh_momentum_tensors()."""
+        self._live_envs_only(self._MOM_WHAT)
+        self.scene.actor_index(actor_name)
+        if self._momentum is None:
+            self._momentum = torch.zeros((self.num_envs, capi.MOMENTUM_FLOATS), dtype=torch.float32, device=self.device)
+        return self._momentum
+
+    def refresh_momentum_tensors(self) -> None:
+        self._live_envs_only(self._MOM_WHAT)
+        if self._momentum is not None:
+            self._physics_call(self._lib.mppi_sim_momentum, _dev_ptr(self._momentum), what=self._MOM_WHAT)
+
+    def _fresh_momentum(self):
+        t = self.acquire_momentum_tensor(self.scene.robot.name)
+        self.refresh_momentum_tensors()
+        return t
+
+    def centre_of_mass(self):
+        """[K, 3]: the robot's centre of mass now (a view of the refreshed momentum tensor)"""
+        return self._fresh_momentum()[:, 1:4]
+
+    def robot_momentum(self):
+        """[K, 6]: linear momentum, then angular momentum about the centre of mass"""
+        return self._fresh_momentum()[:, 4:10]
+
+    def kinetic_energy(self):
+        """[K]"""
+        return self._fresh_momentum()[:, 10]
+
+    def potential_energy(self):
+        """[K]: -m g . c with the model's gravity, 0 without"""
+        return self._fresh_momentum()[:, 11]
+
+    def acquire_centroidal_matrix_tensor(self, actor_name: str):
+        """[K, 6, n_dof] of a fixed-base robot: A @ qd = columns 4:10 of the momentum tensor.  Zero until
+        refresh_centroidal_matrix_tensors()."""
+        self._live_envs_only(self._MOM_WHAT)
+        self.scene.actor_index(actor_name)
+        if self._centroidal_matrix is None:
+            self._centroidal_matrix = torch.zeros((self.num_envs, 6, self.scene.n_dof), dtype=torch.float32, device=self.device)
+        return self._centroidal_matrix
+
+    def acquire_floating_centroidal_matrix_tensor(self, actor_name: str):
+        """[K, 6, 6 + n_dof] of a robot with a moving base: A @ (root linvel, root angvel, qd) = columns 4:10 of the momentum tensor.
+        Zero until refresh_floating_centroidal_matrix_tensors()."""
+        self._live_envs_only(self._MOM_WHAT)
+        self.scene.actor_index(actor_name)
+        if self._floating_centroidal_matrix is None:
+            self._floating_centroidal_matrix = torch.zeros((self.num_envs, 6, 6 + self.scene.n_dof), dtype=torch.float32, device=self.device)
+        return self._floating_centroidal_matrix
+
+    def refresh_centroidal_matrix_tensors(self) -> None:
+        self._live_envs_only(self._MOM_WHAT)
+        if self._centroidal_matrix is not None:
+            self._physics_call(self._lib.mppi_sim_centroidal_matrix, _dev_ptr(self._centroidal_matrix), what=self._MOM_WHAT)
+
+    def refresh_floating_centroidal_matrix_tensors(self) -> None:
+        self._live_envs_only(self._MOM_WHAT)
+        if self._floating_centroidal_matrix is not None:
+            self._physics_call(self._lib.mppi_sim_floating_centroidal_matrix, _dev_ptr(self._floating_centroidal_matrix), what=self._MOM_WHAT)
+
+    def com_jacobian(self, actor_name: str):
+        """a fresh [K, 3, n_dof] (fixed base) or [K, 3, 6 + n_dof] (moving base) Jacobian of the centre of mass: rows 0:3 of the
+        centroidal momentum matrix divided by the mass"""
+        self._live_envs_only(self._MOM_WHAT)
+        self.scene.actor_index(actor_name)
+        moving = not self._c_model.actors[int(self._c_model.robot_actor)].fixed
+        A = torch.empty((self.num_envs, 6, (6 if moving else 0) + self.scene.n_dof), dtype=torch.float32, device=self.device)
+        m = torch.empty((self.num_envs, capi.MOMENTUM_FLOATS), dtype=torch.float32, device=self.device)
+        self._physics_call(self._lib.mppi_sim_floating_centroidal_matrix if moving else self._lib.mppi_sim_centroidal_matrix, _dev_ptr(A), what=self._MOM_WHAT)
+        self._physics_call(self._lib.mppi_sim_momentum, _dev_ptr(m), what=self._MOM_WHAT)
+        return A[:, 0:3, :] / m[:, 0, None, None]
 
     # ------------------------------------------------------------------ inverse dynamics and bias forces of a robot with a moving base
     # tau = M v' + C v + g in the generalised velocity above, [K, 6 + n_dof]: rows 0:3 the force on the base, rows 3:6 the moment
